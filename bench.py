@@ -7,8 +7,22 @@ edges), inputs resident in HBM. The timed region is K such steps (synchronous bo
 initial guess, iterations 1..K of the solve (default 50, the reference UI's batch; the world converges,
 so any K runs positive definite). ``value`` = observations (bearings + odometry edges)
 per second of the J+H build *as it runs inside those steps* (device realtime stamps written by the
-step's own kernels, median over the K steps, the slowest rank); ``ms_per_step`` is that J+H time
-(= roofline.kernel_ms). The steps' wall rate is ``gn_iters_per_s``.
+step's own kernels, median over the K steps, the slowest rank); that J+H time is ``jh_ms_per_step``
+(= roofline.kernel_ms). ``ms_per_step`` is the wall time of one timed step (the timed region / K),
+and ``gn_iters_per_s`` its inverse.
+
+A plain run (``--gpus N --steps K --warmup W``) does only what that headline needs: it builds the
+world and the handle, warms up, times the K steps, writes the outputs if asked and prints the line.
+``--dump-outputs DIR`` writes what the timed path computed in its last step as ``DIR/<name>.npy``
+(float64): the state a caller reads after it (``pose_xyt``, ``landmark_xy``), every timed step's
+``chi2`` / ``n_robust`` / ``max_abs_dx`` and, on one GPU, the last step's ``dx``, ``b`` and a fixed
+seeded sample of the lower triangle of H (``H_lower_values``). The world is seeded, so the same
+arguments give the same inputs in every run and two builds can be compared array by array.
+
+Every other measurement runs only with ``--full`` (the keys stay on the line, null without it): the
+C-loop, batched and façade GN rates, the J+H alone (warm replay, cold caches), the other solver
+ordering, the solver bound model, the triangulation, the CPU baselines, and at N > 1 the per-rank
+phases and the observations partition. ``--steps 0`` (profiling the J+H builds alone) needs it.
 
 With ``--gpus N > 1`` the same world is split over N ranks (strong scaling), one process per GPU:
 under torch.distributed.run (RANK / WORLD_SIZE set), or — without a launcher — this script starts the N
@@ -24,14 +38,16 @@ replicated top: its J+H builds only the H its fronts read, two all-gathers per i
 star's partition (BOS_PARTITION_OBSERVATIONS: the J+H lanes split by measurement order, one
 all-reduce of (H, b), the solve replicated) is timed beside it (``partition_observations``).
 
-Also reported: the J+H kernel's HBM roofline fraction (in-step; from cold caches by events; back to
-back), GN iterations/s, and the CPU baselines (the oracle, oracle/bos_oracle.cpp, and the build's
-C++ CPU backend, timed on this host's usable cores).
+Also reported: the J+H kernel's HBM roofline fraction (in-step; with ``--full`` from cold caches by
+events and back to back), GN iterations/s, and with ``--full`` the CPU baselines (the oracle,
+oracle/bos_oracle.cpp, and the build's C++ CPU backend, timed on this host's usable cores).
 
 ``--config c2`` times BASELINE config 2 instead (synthetic 1k / 2k / 20k, fp64, one GPU): microseconds
-per GN iteration and per J+H build beside the CPU backend's (the size is launch-bound: no roofline).
+per GN iteration and per J+H build, with ``--full`` beside the C loop, the batched loop, the other
+ordering and the CPU backend's (the size is launch-bound: no roofline).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--precision fp32|fp64] [--config c3|c2]
+                    [--dump-outputs DIR] [--full]
 """
 import argparse
 import json
@@ -55,6 +71,48 @@ CONFIG3 = dict(num_poses=100000, num_landmarks=200000, bearings_per_pose=10, see
 
 def log(*a):
     print(*a, file=sys.stderr, flush=True)
+
+
+DUMP_MAX_BYTES = 64 << 20     # --dump-outputs: all files together
+DUMP_MAX_ELEMS = 1 << 20      # per array; a larger one is sampled
+DUMP_SEED = 0xB05D0A7
+
+
+def capture_outputs(S, stats, system):
+    """--dump-outputs: what a caller of the timed path holds after its last step. The state it reads
+    (bos_get_state), every timed step's returned statistics and, where the handle holds the whole
+    system (system: one GPU), the last step's dx, b and the lower triangle of H (bos_get_last_dx,
+    bos_export_system). Called after the timed region, before the state is reset."""
+    pose, lm = S.get_state()
+    out = {"pose_xyt": pose, "landmark_xy": lm}
+    for key in ("chi2", "n_robust", "max_abs_dx"):
+        out[key] = np.array([g[key] for g in stats], dtype=np.float64)
+    if system:
+        out["dx"] = S.last_dx()
+        _, _, vals, b = S.export_system()
+        out["b"] = b
+        out["H_lower_values"] = vals
+    return out
+
+
+def write_outputs(directory, arrays):
+    """Write `arrays` as directory/<name>.npy in float64. An array of more than DUMP_MAX_ELEMS
+    elements is cut to a sample of that many (flat indices drawn once from DUMP_SEED and the array's
+    size, ascending: the same elements in every run). Returns {name: [elements written, of]}."""
+    os.makedirs(directory, exist_ok=True)
+    written, total = {}, 0
+    for name, a in sorted(arrays.items()):
+        full = np.ascontiguousarray(a, dtype=np.float64)
+        a = full
+        if a.size > DUMP_MAX_ELEMS:
+            idx = np.random.default_rng([DUMP_SEED, a.size]).choice(a.size, DUMP_MAX_ELEMS, replace=False)
+            a = a.reshape(-1)[np.sort(idx)]
+        total += a.nbytes
+        if total > DUMP_MAX_BYTES:
+            raise RuntimeError(f"--dump-outputs: more than {DUMP_MAX_BYTES} bytes to write")
+        np.save(os.path.join(directory, name + ".npy"), a)
+        written[name] = [int(a.size), int(full.size)]
+    return written
 
 
 def host_cpus():
@@ -380,9 +438,10 @@ def bench_c2(args):
     """BASELINE config 2 on one GPU: the synthetic 1k-pose / 2k-landmark / 20k-bearing
     world the GPU parity tests check (bos.synthetic(1000, 2000, 20)), fp64 J+H and solve. At this size the
     step is launch- and latency-bound (1.7 MB of J+H traffic), so the line reports microseconds: per GN
-    iteration (synchronous bos_step, the Python loop and the C loop; bos_step_n batches), the in-step
-    phases (device stamps) and the J+H build back to back, beside the build's C++ CPU backend (full GN
-    iterations on 1 thread and on every usable CPU) and the oracle's J+H on the same host."""
+    iteration (synchronous bos_step in the Python loop) and the in-step phases (device stamps); with
+    --full (bench_c2_full) also the C loop, bos_step_n batches and the J+H build back to back, beside
+    the build's C++ CPU backend (full GN iterations on 1 thread and on every usable CPU) and the
+    oracle's J+H on the same host."""
     global bos
     import bos as _bos
     bos = _bos
@@ -402,8 +461,38 @@ def bench_c2(args):
     S.synchronize()
     wall = time.perf_counter() - t0
     assert all(g["solver_info"] == 0 for g in stats), "non-positive pivot in a timed C2 step"
+    dumped = write_outputs(args.dump_outputs, capture_outputs(S, stats, True)) if args.dump_outputs else None
     S.set_state(*init)
     ph = {key: float(np.median([g[key] for g in stats])) for key in ("t_linearize_ms", "t_solve_ms", "t_update_ms")}
+    gn_us = wall * 1e6 / k
+    line = {
+        "metric": METRIC, "value": nobs / (ph["t_linearize_ms"] * 1e-3), "unit": "obs/s", "n_gpus": 1, "steps": k,
+        "warmup": max(args.warmup, 20), "ms_per_step": gn_us * 1e-3, "jh_ms_per_step": ph["t_linearize_ms"],
+        "higher_is_better": True, "full": args.full,
+        "scaling": "strong", "vs_baseline": None, "dtype": "f64" if precision == bos.BOS_FP64 else "f32",
+        "data": "synthetic",
+        "config": {"workload": "config 2: synthetic 1k poses / 2k landmarks / 20k bearings / 999 odometry edges "
+                               "(bos.synthetic(1000, 2000, 20), the GPU parity tests' world); J+H and solve "
+                               + args.precision + ", schur", "poses": P.NP, "landmarks": P.NL,
+                   "bearings": int(len(P.b_z)), "odometry": int(len(P.o_z)), "parallelism": "single GPU"},
+        "note": "launch-bound size (SURVEY.md §8(d)): microseconds per iteration, no roofline",
+        "gn_us_per_iteration": gn_us, "gn_iters_per_s": 1e6 / gn_us,
+        "gn_phase_us": {key.replace("_ms", "_us"): v * 1e3 for key, v in ph.items()},
+        "jh_us_in_step": ph["t_linearize_ms"] * 1e3,
+        "dumped_outputs": dumped,
+        "libbos_sha256": lib_sha256(),
+    }
+    if args.full:
+        line.update(bench_c2_full(args, P, S, init, precision, gn_us, ph))
+    S.close()
+    print(json.dumps(line), flush=True)
+    return 0
+
+
+def bench_c2_full(args, P, S, init, precision, gn_us, ph):
+    """--config c2 --full: the other GN loops on the handle S (C loop, bos_step_n batches), the J+H
+    back to back, the other ordering and the CPU baselines; the keys they add to the line."""
+    k = args.steps
     c_loop_ms = S.time_steps(k)
     S.set_state(*init)
     tb = time.perf_counter()
@@ -413,7 +502,6 @@ def bench_c2(args):
     assert last["solver_info"] == 0
     S.set_state(*init)
     warm_ms = S.time_linearize(max(args.replay_steps, 200))
-    S.close()
     # the other multifrontal ordering (nested dissection, landmarks not folded) on the same world
     S2 = bos.Solver(P, precision=precision, solver=bos.BOS_SOLVER_SUPERNODAL, device=0)
     for _ in range(5):
@@ -447,31 +535,16 @@ def bench_c2(args):
         O.linearize(Q, precision=64 if precision == bos.BOS_FP64 else 32)
         n += 1
     oracle_jh_us = (time.perf_counter() - tc) * 1e6 / n
-    gn_us = wall * 1e6 / k
-    line = {
-        "metric": METRIC, "value": nobs / (ph["t_linearize_ms"] * 1e-3), "unit": "obs/s", "n_gpus": 1, "steps": k,
-        "warmup": max(args.warmup, 20), "ms_per_step": ph["t_linearize_ms"], "higher_is_better": True,
-        "scaling": "strong", "vs_baseline": None, "dtype": "f64" if precision == bos.BOS_FP64 else "f32",
-        "data": "synthetic",
-        "config": {"workload": "config 2: synthetic 1k poses / 2k landmarks / 20k bearings / 999 odometry edges "
-                               "(bos.synthetic(1000, 2000, 20), the GPU parity tests' world); J+H and solve "
-                               + args.precision + ", schur", "poses": P.NP, "landmarks": P.NL,
-                   "bearings": int(len(P.b_z)), "odometry": int(len(P.o_z)), "parallelism": "single GPU"},
-        "note": "launch-bound size (SURVEY.md §8(d)): microseconds per iteration, no roofline",
-        "gn_us_per_iteration": gn_us, "gn_iters_per_s": 1e6 / gn_us,
+    return {
         "gn_us_per_iteration_c_loop": c_loop_ms * 1e3, "gn_us_per_iteration_batched": batched_ms * 1e3,
-        "gn_phase_us": {key.replace("_ms", "_us"): v * 1e3 for key, v in ph.items()}, "gn_other": other,
-        "jh_us_in_step": ph["t_linearize_ms"] * 1e3, "jh_us_back_to_back": warm_ms * 1e3,
+        "gn_other": other, "jh_us_back_to_back": warm_ms * 1e3,
         "cpu_baseline_gn": {"us_per_iteration": cpu_best, "forms_us_per_iteration": cpu, "kind": "port",
                             "sample": "full GN iterations of config 2 by the build's C++ CPU backend (fp64 J+H, host "
                                       "multifrontal Cholesky, box-plus), >= 3 s per thread count", "host": cpus},
         "cpu_baseline_jh": {"us_per_build": oracle_jh_us, "cores": 1, "kind": "port",
                             "sample": "the C++ oracle's J+H of config 2 in reference order, >= 2 s"},
         "gn_speedup_vs_cpu": cpu_best / gn_us, "jh_speedup_vs_cpu": oracle_jh_us / (ph["t_linearize_ms"] * 1e3),
-        "libbos_sha256": lib_sha256(),
     }
-    print(json.dumps(line), flush=True)
-    return 0
 
 
 def main():
@@ -479,6 +552,13 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50, help="GN iterations timed (from the initial guess)")
     ap.add_argument("--warmup", type=int, default=5, help="untimed GN iterations before the timed ones")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what their last step computed as DIR/<name>.npy (float64, at "
+                         "most 64 MB: the state, the steps' statistics and on one GPU dx, b and a seeded sample of H)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every secondary measurement (other GN loops, J+H alone warm and cold, the other "
+                         "ordering, triangulation, CPU baselines, N > 1: per-rank phases and the observations "
+                         "partition); without it only the headline's timed steps run")
     ap.add_argument("--device-warmup", type=int, default=1000,
                     help="untimed GN iterations (bos_step_n batches of 100, about 0.5 s on one GPU) before the "
                          "headline's warmup: brings the GPU to its steady clocks (tools/jh_placement_probe.py); "
@@ -521,6 +601,16 @@ def main():
 
     if args.precision is None:
         args.precision = "fp64" if args.config == "c2" else "fp32"
+    if not args.full and not args.check_launch:
+        # a plain run: the headline's timed steps only
+        if args.steps <= 0:
+            log("error: --steps 0 (the J+H builds alone) needs --full")
+            sys.exit(2)
+        args.replay_steps = args.cold_steps = args.tri_steps = 0
+        args.no_cpu_baseline = args.no_gn_other = args.no_partition_other = True
+    if args.dump_outputs and args.steps <= 0:
+        log("error: --dump-outputs needs timed steps (--steps > 0)")
+        sys.exit(2)
     if args.config == "c2":
         if args.gpus != 1:
             log("error: --config c2 runs on one GPU")
@@ -672,14 +762,17 @@ def main():
         except Exception as e:
             log(f"rank {rank}: {getattr(fn, '__name__', fn)}: {e}")
 
-    def timed_steps(h, partition, k, warmup, mode, device_warmup=0):
+    outputs = {}   # --dump-outputs: rank 0's arrays of the headline's last timed step
+
+    def timed_steps(h, partition, k, warmup, mode, device_warmup=0, capture=False):
         """`device_warmup` untimed GN iterations as one batch (not with the gloo exchange), `warmup`
         untimed GN iterations, then the state reset to the initial guess (outside the
         timed region) and k GN iterations from it, timed as one region: iterations 1..k of the solve
         (the world converges; tests/test_gpu_c3_gn.py checks 200 fp32 iterations positive definite).
         Collective-safe (N > 1): a local failure stops this rank's stepping but not its barriers and
         reductions, so every rank leaves together. Returns (wall seconds of the timed steps, max over
-        ranks; per-step stats; the local error or None)."""
+        ranks; per-step stats; the local error or None). capture: keep what the last timed step left
+        (capture_outputs) in `outputs` before the reset."""
         err, init, stats = None, None, []
         try:
             init = h.get_state()
@@ -706,6 +799,12 @@ def main():
         barrier()
         quiet(h.synchronize)
         wall = max_over_ranks(time.perf_counter() - t0)
+        if capture and err is None:   # before the reset: the state the last timed step left
+            try:
+                outputs.clear()
+                outputs.update(capture_outputs(h, stats, world == 1))
+            except Exception as e:
+                err = f"output capture: {type(e).__name__}: {e}"
         if init is not None:
             quiet(h.set_state, *init)
         bad = [i + 1 for i, g in enumerate(stats) if g["solver_info"] != 0]
@@ -723,7 +822,7 @@ def main():
         dist.all_reduce(hi, op=dist.ReduceOp.MAX)
         return bool(torch.equal(lo, hi))
 
-    def check_and_time(mode, hinf, partition, k, warmup, device_warmup):
+    def check_and_time(mode, hinf, partition, k, warmup, device_warmup, capture=False):
         """One exchange mode's run (collective-safe; raises at the end on a local or global failure):
         the direct exchange connected (every rank maps every other rank's mailbox), three GN steps from
         the initial guess giving every rank the same chi^2 (each rank combines all ranks' headers, so a
@@ -762,7 +861,7 @@ def main():
             err = "the ranks' chi^2 differ over three GN steps"
         if not agree_all(dist, torch, err is None)[0]:
             raise RuntimeError(err or "the check failed on another rank")
-        wall, stats, err = timed_steps(h, partition, k, warmup, mode, device_warmup)
+        wall, stats, err = timed_steps(h, partition, k, warmup, mode, device_warmup, capture)
         vals = [g["chi2"] for g in stats] if err is None and len(stats) == k else [float("nan")] * k
         same = chi2_agree(vals)
         if err is None and not same:
@@ -783,7 +882,8 @@ def main():
         modes,
         setup=lambda m: make_handle(bos.BOS_PARTITION_SUBTREE, m),
         run=lambda m, hi: check_and_time(m, hi, bos.BOS_PARTITION_SUBTREE, args.steps, args.warmup,
-                                         args.device_warmup) if args.steps > 0 or world > 1 else (0.0, []),
+                                         args.device_warmup, bool(args.dump_outputs) and rank == 0)
+        if args.steps > 0 or world > 1 else (0.0, []),
         agree=lambda ok, why: agree_all(dist, torch, ok, why),
         close=close_handle, log=log)
     if mode is None:
@@ -800,6 +900,7 @@ def main():
         if args.exchange != mode:
             exchange_reason += f" (--exchange {args.exchange} failed, see attempts)"
     wall, stats = res
+    dumped = write_outputs(args.dump_outputs, outputs) if args.dump_outputs and rank == 0 else None
     phase, jh_ms, gn_it_s = None, None, None
     ranks_consistent = True if world > 1 and args.steps > 0 else None
     per_rank = None
@@ -838,7 +939,7 @@ def main():
     if args.steps > 0:
         phase = phases(stats)
         jh_ms = max_over_ranks(phase["t_linearize_ms"])      # the slowest rank's in-step J+H
-        if world > 1:
+        if world > 1 and args.full:
             per_rank = rank_breakdown(S, partition=bos.BOS_PARTITION_SUBTREE)
         gn_it_s = args.steps / wall
         log(f"rank {rank}: {args.steps} GN steps in {wall * 1e3:.1f} ms ({gn_it_s:.0f} it/s); phases {phase}")
@@ -858,8 +959,8 @@ def main():
 
     # ---- other GN loops (the headline's timed region above is the reference for value)
     gn_c_loop, gn_batched = None, None
-    init = S.get_state()
-    if args.steps > 0 and mode != "gloo":
+    if args.full and args.steps > 0 and mode != "gloo":
+        init = S.get_state()
         c_ms = max_or_none(local(lambda: S.time_steps(min(args.steps, 50)), "C-loop steps"))   # bos_step in a C loop
         gn_c_loop = 1e3 / c_ms if c_ms else None
         local(lambda: S.set_state(*init), "state reset")
@@ -881,7 +982,7 @@ def main():
     # ---- the drop-in caller's loop: proj02::Solver::step() through the C++ façade, as the reference's
     # executable calls it (executables/bearing_only_slam.cpp:93-99), then one read of solver.state
     facade = None
-    if world == 1 and args.steps > 0:
+    if args.full and world == 1 and args.steps > 0:
         nf = min(args.steps, 50)
         f = bos.time_facade_steps(P, nf, bos.options(solver=solver, precision=precision, lanes_per_pose=lpp))
         facade = {"steps": nf, "ms_per_step": f["ms_per_step"], "ms_state_read": f["ms_state_read"],
@@ -893,7 +994,8 @@ def main():
             f"handle {1e3 / f['ms_per_step_capi']:.0f} it/s")
 
     # ---- the J+H alone: back to back (warm replay) and from cold caches (events)
-    barrier()
+    if args.full:
+        barrier()
     replay_ms = max_or_none(local(lambda: S.time_linearize(args.replay_steps), "warm J+H")) \
         if args.replay_steps > 0 else None
     cold_ms = max_or_none(local(lambda: S.time_linearize(args.cold_steps, flush_caches=True), "cold J+H")) \
@@ -988,8 +1090,12 @@ def main():
             "steps": args.steps,
             "warmup": args.warmup,
             "device_warmup": args.device_warmup if args.steps > 0 else 0,
-            "ms_per_step": head_ms,
+            # wall time of one timed GN step; the J+H time inside it (value = nobs / it) beside it
+            "ms_per_step": wall * 1e3 / args.steps if args.steps > 0 else head_ms,
+            "jh_ms_per_step": head_ms,
             "higher_is_better": True,
+            "full": args.full,
+            "dumped_outputs": dumped,
             "scaling": "strong",
             "vs_baseline": None,
             "dtype": "f32" if precision == bos.BOS_FP32 else "f64",
@@ -1021,7 +1127,7 @@ def main():
             "gn_iters_per_s_facade": 1e3 / facade["ms_per_step"] if facade else None,
             "facade": facade,
             "gn_phase_ms": phase,
-            "solver_model": solver_model(P, phase, world),
+            "solver_model": solver_model(P, phase, world) if args.full else None,
             "gn_solver": args.solver,
             "gn_other": gn_other,
             "partition_observations": part_obs,

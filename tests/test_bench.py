@@ -65,6 +65,67 @@ def test_traffic_only_from_a_profile_of_this_build(tmp_path):
     assert t == {"instep": None, "warm": None}
 
 
+def test_dump_writer_samples_large_arrays_the_same_way_every_time(tmp_path, monkeypatch):
+    """--dump-outputs: arrays are written whole as float64 up to the element cap; a larger one is cut
+    to a sample of exactly that many elements, the same (ascending) flat indices in every run, and the
+    byte limit over all files is enforced."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.setattr(bench, "DUMP_MAX_ELEMS", 100)
+    small = np.arange(60, dtype=np.float32).reshape(20, 3)
+    big = np.arange(1000, dtype=np.float64) * 0.5
+    for d in ("a", "b"):
+        w = bench.write_outputs(str(tmp_path / d), {"small": small, "big": big})
+        assert w == {"small": [60, 60], "big": [100, 1000]}
+    a, b = (np.load(tmp_path / d / "big.npy") for d in ("a", "b"))
+    assert a.dtype == np.float64 and a.shape == (100,) and np.array_equal(a, b)
+    assert np.all(np.diff(a) > 0) and set(a) <= set(big) and not np.array_equal(a, big[:100])
+    s = np.load(tmp_path / "a" / "small.npy")
+    assert s.dtype == np.float64 and np.array_equal(s, small)
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 8 * 150)
+    with pytest.raises(RuntimeError, match="--dump-outputs"):
+        bench.write_outputs(str(tmp_path / "c"), {"small": small, "big": big})
+
+
+def test_plain_run_refuses_steps_0():
+    """Without --full only the timed GN steps run, so --steps 0 (the J+H builds alone, a --full leg)
+    is refused before anything is set up."""
+    r = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--steps", "0", "--warmup", "0"], capture_output=True,
+                       text=True, timeout=120, env=_env())
+    assert r.returncode == 2 and "--full" in r.stderr
+
+
+@pytest.mark.gpu
+def test_plain_c2_run_dumps_the_same_outputs_twice(tmp_path):
+    """A plain run (config 2, the small world) prints ms_per_step as the wall time of one timed step,
+    leaves the --full keys out, and --dump-outputs writes the last timed step's results: float64,
+    finite, of the world's sizes, and equal bit for bit between two runs with the same arguments."""
+    import numpy as np
+    runs = []
+    for d in ("a", "b"):
+        r = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--steps", "7", "--warmup", "2", "--config", "c2",
+                            "--dump-outputs", str(tmp_path / d)], capture_output=True, text=True, timeout=120,
+                           env=_env())
+        assert r.returncode == 0, r.stderr[-2000:]
+        line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+        assert line["steps"] == 7 and line["full"] is False and "cpu_baseline_gn" not in line
+        assert abs(line["ms_per_step"] * 1e3 - line["gn_us_per_iteration"]) < 1e-6
+        assert line["value"] > 0 and 0 < line["jh_ms_per_step"] < line["ms_per_step"]
+        runs.append({f[:-4]: np.load(tmp_path / d / f) for f in sorted(os.listdir(tmp_path / d))})
+    a, b = runs
+    n = 3 * 1000 + 2 * 2000
+    assert {k: v.shape for k, v in a.items() if k != "H_lower_values"} == {
+        "pose_xyt": (1000, 3), "landmark_xy": (2000, 2), "chi2": (7,), "n_robust": (7,), "max_abs_dx": (7,),
+        "dx": (n,), "b": (n,)}
+    assert a["H_lower_values"].ndim == 1 and a["H_lower_values"].size > 20000
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    for k in a:
+        assert a[k].dtype == np.float64 and np.all(np.isfinite(a[k])), k
+        assert np.array_equal(a[k], b[k]), k
+    assert a["chi2"][-1] < a["chi2"][0] and np.any(a["dx"] != 0)
+
+
 LADDER_CASES = [
     # (world, failures, expected mode, expected failed attempts)
     (2, "", "p2p", []),

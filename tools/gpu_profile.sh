@@ -11,12 +11,12 @@ export TMPDIR=/tmp
 TAG=${1:-r03}
 O=gpurun_out/prof_$TAG
 mkdir -p $O
-INSTEP="--replay-steps 0 --cold-steps 0 --no-cpu-baseline --no-gn-other --tri-steps 0"
+INSTEP="--full --replay-steps 0 --cold-steps 0 --no-cpu-baseline --no-gn-other --tri-steps 0"
 for P in fp32 fp64; do
   timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/trace_${P}_instep -o run --output-format csv -- \
     python3 bench.py $INSTEP --precision $P > $O/bench_${P}_instep.json 2> $O/bench_${P}_instep.err || exit 1
   for MODE in instep warm; do
-    if [ $MODE = instep ]; then ARGS="$INSTEP"; else ARGS="--steps 0 --warmup 0 --replay-steps 20 --cold-steps 0 --no-cpu-baseline --no-gn-other --tri-steps 0"; fi
+    if [ $MODE = instep ]; then ARGS="$INSTEP"; else ARGS="--full --steps 0 --warmup 0 --replay-steps 20 --cold-steps 0 --no-cpu-baseline --no-gn-other --tri-steps 0"; fi
     i=0
     for C in "TCC_EA0_RDREQ_32B_sum TCC_EA0_RDREQ_64B_sum TCC_EA0_RDREQ_128B_sum TCC_EA0_RDREQ_sum" \
              "TCC_EA0_WRREQ_sum TCC_EA0_WRREQ_64B_sum" \
@@ -35,6 +35,6 @@ print((36 if '$P' == 'fp32' else 64) * len(P.b_z) + (80 if '$P' == 'fp32' else 1
   done
 done
 timeout -k 10 600 rocprofv3 --kernel-trace --stats -d $O/trace_fp32_default -o run --output-format csv -- \
-  python3 bench.py > $O/bench_fp32_default.json 2> $O/bench_fp32_default.err || exit 1
+  python3 bench.py --full > $O/bench_fp32_default.json 2> $O/bench_fp32_default.err || exit 1
 python3 tools/step_timeline.py $O/trace_fp32_default > $O/gn_step_timeline.txt || exit 1
 timeout -k 10 180 python3 tools/solver_stamps.py > $O/solver_stamps.txt 2> $O/solver_stamps.err || exit 1

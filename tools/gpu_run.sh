@@ -22,10 +22,14 @@
 # Library variants are built on the CPU side first (tools/build_rev_variant.sh, or a copy of
 # lib/libbos.so) into gpurun_exp/. Outputs land in gpurun_out/<step>*. The profile set is
 # tools/gpu_profile.sh; smoke + tests + profile set tools/gpu_round.sh.
+# The bench lines of `bench`, `final` and `c2` (bench.py --full: every measurement, not only the
+# headline's timed steps) land in $OUT (default bench_out/).
 set -o pipefail
 cd $GRAFT_REPO_ROOT
 export TMPDIR=/tmp
 mkdir -p gpurun_out
+OUT=${OUT:-bench_out}
+mkdir -p $OUT
 step=$1
 shift
 case $step in
@@ -46,9 +50,9 @@ case $step in
       timeout -k 10 800 python -u -m pytest ${@:-tests} -m gpu -x -v --timeout 400 --timeout-method thread \
         -p no:cacheprovider > gpurun_out/pytest_gpu.log 2>&1 ;;
   bench)
-    timeout -k 10 600 python bench.py > gpurun_out/bench.json 2> gpurun_out/bench.err ;;
+    timeout -k 10 600 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err ;;
   rehearse)
-    timeout -k 10 400 python bench.py --gpus 2 --same-device --steps 20 --warmup 3 --no-cpu-baseline --no-gn-other \
+    timeout -k 10 400 python bench.py --full --gpus 2 --same-device --steps 20 --warmup 3 --no-cpu-baseline --no-gn-other \
       --tri-steps 0 --replay-steps 0 --cold-steps 0 --no-partition-other > gpurun_out/bench2.json 2> gpurun_out/bench2.err ;;
   probes)
     timeout -k 10 60 ./tools/rccl_latency > gpurun_out/rccl_latency.txt 2>&1 &&
@@ -58,29 +62,29 @@ case $step in
     timeout -k 10 180 python -c "import __graft_entry__ as g; g.smoke()" > gpurun_out/final_smoke.log 2>&1 &&
       timeout -k 10 700 python -u -m pytest tests -m gpu -x -v --timeout 400 --timeout-method thread -p no:cacheprovider \
         > gpurun_out/final_gpu_suite.log 2>&1 &&
-      timeout -k 10 400 python bench.py > gpurun_out/final_bench_fp32.json 2> gpurun_out/final_bench_fp32.err &&
-      timeout -k 10 400 python bench.py --precision fp64 --no-cpu-baseline > gpurun_out/final_bench_fp64.json \
-        2> gpurun_out/final_bench_fp64.err &&
+      timeout -k 10 400 python bench.py --full > $OUT/final_bench_fp32.json 2> $OUT/final_bench_fp32.err &&
+      timeout -k 10 400 python bench.py --full --precision fp64 --no-cpu-baseline > $OUT/final_bench_fp64.json \
+        2> $OUT/final_bench_fp64.err &&
       bash tools/gpu_profile.sh $1 > gpurun_out/final_profile.log 2>&1 ;;
   c2)
-    timeout -k 10 300 python bench.py --config c2 > gpurun_out/bench_c2.json 2> gpurun_out/bench_c2.err ;;
+    timeout -k 10 300 python bench.py --full --config c2 > $OUT/bench_c2.json 2> $OUT/bench_c2.err ;;
   c2trace)
     lib=${1:-prb-project-bearing-only-slam_amd/lib/libbos.so}
     BOS_LIB=$lib timeout -k 10 180 rocprofv3 --kernel-trace --output-format csv -d gpurun_out/trace_c2 -- \
       python3 tools/c2_steps.py 20 > gpurun_out/trace_c2.log 2>&1 &&
       python3 tools/c2_timeline.py gpurun_out/trace_c2 > gpurun_out/c2_timeline.txt 2>&1 ;;
   ladder)
-    FLAGS="--same-device --steps 20 --warmup 3 --no-cpu-baseline --no-gn-other --tri-steps 0 --replay-steps 20 --cold-steps 0"
+    FLAGS="--full --same-device --steps 20 --warmup 3 --no-cpu-baseline --no-gn-other --tri-steps 0 --replay-steps 20 --cold-steps 0"
     timeout -k 10 400 python bench.py --gpus 2 $FLAGS > gpurun_out/ladder_p2p.json 2> gpurun_out/ladder_p2p.err &&
       timeout -k 10 400 python bench.py --gpus 2 --exchange rccl $FLAGS > gpurun_out/ladder_rccl.json \
         2> gpurun_out/ladder_rccl.err ;;
   p2p8)
     timeout -k 10 500 python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 \
-      --master-port 29517 bench.py --gpus 8 --same-device --steps 30 --warmup 5 --no-cpu-baseline \
+      --master-port 29517 bench.py --full --gpus 8 --same-device --steps 30 --warmup 5 --no-cpu-baseline \
       > gpurun_out/p2p8.json 2> gpurun_out/p2p8.err ;;
   l2hit)
-    INSTEP="--replay-steps 0 --cold-steps 0 --no-cpu-baseline --no-gn-other --tri-steps 0"
-    WARM="--steps 0 --warmup 0 --replay-steps 20 --cold-steps 0 --no-cpu-baseline --no-gn-other --tri-steps 0"
+    INSTEP="--full --replay-steps 0 --cold-steps 0 --no-cpu-baseline --no-gn-other --tri-steps 0"
+    WARM="--full --steps 0 --warmup 0 --replay-steps 20 --cold-steps 0 --no-cpu-baseline --no-gn-other --tri-steps 0"
     timeout -s KILL 180 rocprofv3 --pmc TCC_HIT_sum TCC_MISS_sum --kernel-include-regex linearize -d gpurun_out/tcc_instep \
       -o run --output-format csv -- python3 bench.py $INSTEP > gpurun_out/tcc_instep.json 2> gpurun_out/tcc_instep.err &&
       timeout -s KILL 180 rocprofv3 --pmc TCC_HIT_sum TCC_MISS_sum --kernel-include-regex linearize \
