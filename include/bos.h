@@ -254,6 +254,26 @@ int bos_get_state(const struct bos_solver* s, double* pose_xyt, double* landmark
 int bos_set_state(struct bos_solver* s, const double* pose_xyt, const double* landmark_xy);
 /* The dx of the last bos_step in the reference's dof order (slam/solver.cpp:88-94) */
 int bos_get_last_dx(const struct bos_solver* s, double* dx);
+
+/* Marginal covariances of the current estimate: the diagonal blocks of (H_nf)^-1, H_nf being
+ * exactly the matrix bos_linearize builds at the handle's current state with its current kernel
+ * threshold and damping factor (fixed pose removed). H includes the damping term: call
+ * bos_set_damping_factor(0) first for the plain Gauss-Newton information matrix; with zero damping
+ * a landmark seen by a single bearing makes H singular (the reference dataset has three: 69, 112
+ * and 114).
+ * pose_cov [NP * 9] (3 x 3 per pose) and landmark_cov [NL * 4] (2 x 2 per landmark): host
+ * pointers, row-major, stix order; either may be NULL; the fixed pose's block is zeros.
+ * *solver_info (may be NULL): the count of non-positive pivots of the factorization; when it is not
+ * zero the blocks are not meaningful (the call still returns BOS_OK, as bos_step does).
+ * Synchronous. Runs the J+H build, the multifrontal factorization and a selected-inverse pass over
+ * the same assembly tree (no n x n inverse is formed) as individual launches on the handle's stream.
+ * The state is not touched and a following bos_step gives the results it would have given without
+ * the call; the call counts as a bos_linearize for bos_export_system. After it bos_get_last_dx is
+ * unspecified until the next step (here: BOS_ERR_INVALID, as before the first step).
+ * BOS_ERR_UNSUPPORTED on BOS_SOLVER_DENSE_CHOL / BOS_SOLVER_ROCSOLVER_RF handles and on sharded
+ * handles (world_size > 1, a communicator, or external / direct exchange); BOS_ERR_DEVICE (with the
+ * byte count in bos_last_error) when the pass's buffers cannot be allocated: the handle stays usable. */
+int bos_marginals(struct bos_solver* s, double* pose_cov, double* landmark_cov, int32_t* solver_info);
 /* Diagnostics: the phase boundaries of the last completed step, realtime clock (100 MHz ticks),
  * as the step's own kernels stamped them: [0] J+H start, [1] J+H end / solve start, [2] solve end,
  * [3] step end; subtree-sharded handles: [4] phase 0 done (own subtrees factored, exchange 1

@@ -54,7 +54,7 @@ EXPORTED_SYMBOLS = [
     "bos_time_linearize", "bos_time_triangulate", "bos_time_steps", "bos_cpu_gn_create", "bos_cpu_gn_step", "bos_cpu_gn_get_state",
     "bos_cpu_gn_destroy", "bos_normalized_angle_f64", "bos_normalized_angle_f32", "bos_exchange_p2p_handle",
     "bos_exchange_p2p_connect", "bos_time_facade_steps", "bos_debug_facade_selftest", "bos_set_exchange_timeout",
-    "bos_last_step_stamps",
+    "bos_last_step_stamps", "bos_marginals", "bos_plan_mf_marginals", "bos_marginals_timing",
 ]
 
 P2P_HANDLE_BYTES = 64   # include/bos.h BOS_P2P_HANDLE_BYTES
@@ -168,6 +168,9 @@ def lib():
                                             ctypes.c_int32, ctypes.c_int64, _ip, _ip, ctypes.POINTER(ctypes.c_uint8),
                                             ctypes.POINTER(ctypes.c_uint8), _ip, ctypes.POINTER(bos_plan_info)]),
         "bos_plan_mf_selftest": (ctypes.c_int, [ctypes.POINTER(bos_problem), ctypes.POINTER(bos_options), _dp, _dp, _dp]),
+        "bos_plan_mf_marginals": (ctypes.c_int, [ctypes.POINTER(bos_problem), ctypes.POINTER(bos_options), _dp, _dp, _dp]),
+        "bos_marginals": (ctypes.c_int, [vp, _dp, _dp, _ip]),
+        "bos_marginals_timing": (ctypes.c_int, [vp, _dp, ctypes.POINTER(ctypes.c_int64)]),
         "bos_plan_shard_selftest": (ctypes.c_int, [ctypes.POINTER(bos_problem), ctypes.POINTER(bos_options), ctypes.c_int32,
                                                    _dp, _dp, _dp]),
         "bos_plan_node_owner": (ctypes.c_int, [ctypes.POINTER(bos_problem), ctypes.POINTER(bos_options), ctypes.c_int32, _ip]),
@@ -423,6 +426,19 @@ def plan_mf_selftest(P: Problem, vals, rhs, solver: int = BOS_SOLVER_SUPERNODAL,
     _check(lib().bos_plan_mf_selftest(ctypes.byref(cs), ctypes.byref(opt), _ptr(v, ctypes.c_double),
                                       _ptr(b, ctypes.c_double), _ptr(x, ctypes.c_double)), "plan_mf_selftest")
     return x
+
+
+def plan_mf_marginals(P: Problem, vals, solver: int = BOS_SOLVER_SCHUR, schur_leaf: int = 0):
+    """Host selected inverse of the plan's multifrontal factor (test hook): the marginal covariance
+    blocks (pose_cov [NP, 3, 3], lm_cov [NL, 2, 2]) of the H_nf whose stored entries are vals."""
+    cs = P.c_struct()
+    v = np.ascontiguousarray(vals, dtype=np.float64)
+    pose = np.zeros((P.NP, 3, 3))
+    lm = np.zeros((P.NL, 2, 2))
+    opt = options(solver, schur_leaf=schur_leaf)
+    _check(lib().bos_plan_mf_marginals(ctypes.byref(cs), ctypes.byref(opt), _ptr(v, ctypes.c_double),
+                                       _ptr(pose, ctypes.c_double), _ptr(lm, ctypes.c_double)), "plan_mf_marginals")
+    return pose, lm
 
 
 def plan_shard_selftest(P: Problem, world: int, vals, rhs, solver: int = BOS_SOLVER_SCHUR):
@@ -684,6 +700,23 @@ class Solver:
         _check(lib().bos_export_system(self._h, nnz, _ptr(rows, ctypes.c_int32), _ptr(cols, ctypes.c_int32),
                                        _ptr(vals, ctypes.c_double), _ptr(b, ctypes.c_double)), "export_system")
         return rows, cols, vals, b
+
+    def marginals(self, poses: bool = True, landmarks: bool = True):
+        """Marginal covariances of the current estimate (bos_marginals): (pose_cov [NP, 3, 3],
+        lm_cov [NL, 2, 2], solver_info); poses / landmarks False: that output is not asked for (None)."""
+        pose = np.zeros((self.P.NP, 3, 3)) if poses else None
+        lm = np.zeros((self.P.NL, 2, 2)) if landmarks else None
+        info = ctypes.c_int32(0)
+        _check(lib().bos_marginals(self._h, _ptr(pose, ctypes.c_double), _ptr(lm, ctypes.c_double),
+                                   ctypes.byref(info)), "bos_marginals")
+        return pose, lm, info.value
+
+    def marginals_timing(self) -> dict:
+        """The last marginals() call's split in ms and the Sigma-front buffer's bytes (bos_marginals_timing)."""
+        ms = np.zeros(4)
+        nb = ctypes.c_int64(0)
+        _check(lib().bos_marginals_timing(self._h, _ptr(ms, ctypes.c_double), ctypes.byref(nb)), "bos_marginals_timing")
+        return {"jh_ms": ms[0], "factor_ms": ms[1], "selinv_ms": ms[2], "download_ms": ms[3], "sigma_bytes": nb.value}
 
     def get_state(self):
         pose = np.zeros((self.P.NP, 3))

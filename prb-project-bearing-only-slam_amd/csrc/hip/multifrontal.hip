@@ -28,6 +28,7 @@
 
 #include "../host/plan.hpp"
 #include "multifrontal.hpp"
+#include "selinv.hpp"
 
 namespace bos {
 namespace dev {
@@ -2359,6 +2360,7 @@ struct MfDevice {
     unsigned long long *Ug = nullptr, *xg = nullptr;
     int64_t* ug_off = nullptr;
     int8_t* xtag = nullptr;
+    SelInv* selinv = nullptr;     // selected inverse (hip/selinv.hip): built when marginals are first asked for
 
     MfArgs args(const Prog& P, int lev, int c, const double* A, double* x) const {
         MfArgs g;
@@ -2641,6 +2643,7 @@ int mf_create(const Multifrontal& F, const int8_t* owner, int rank, MfDevice** o
 
 void mf_destroy(MfDevice* d) {
     if (!d) return;
+    selinv_destroy(d->selinv);
     free_prog(d->prog[0]);
     free_prog(d->prog[1]);
     void* bufs[] = {d->emap, d->emap_off, d->epoch, d->fid_f, d->fid_b, d->fold_cnt, d->fold_cptr, d->fold_chunk, d->fold_rec, d->parent,
@@ -2804,6 +2807,8 @@ hipError_t mf_solve(MfDevice* d, int which, double* x, hipStream_t s) {
     return hipSuccess;
 }
 
+MfView mf_view(const MfDevice* d) { return MfView{d->k, d->r, d->parent, d->rmap, d->L_off, d->rmap_off, d->L}; }
+SelInv** mf_selinv_slot(MfDevice* d) { return &d->selinv; }
 int32_t* mf_info_ptr(const MfDevice* d) { return d->info; }
 uint32_t* mf_epoch_ptr(const MfDevice* d) { return d->epoch; }
 void mf_debug_set_stamps(MfDevice* d, unsigned long long* stamps) {

@@ -47,6 +47,17 @@ constexpr int32_t kMfStall = 1 << 30;
 // ticket zero (the last wave out resets it)
 int32_t* mf_tickets_ptr(const MfDevice* d);
 constexpr int kMfTickets = 3;
+// What the selected inverse (hip/selinv.hpp) reads of a handle: the static tree arrays and the L
+// panels of the last mf_factor; and the slot where its state hangs (null until marginals are first
+// asked for; mf_destroy frees it)
+struct MfView {
+    const int32_t *k, *r, *parent, *rmap;
+    const int64_t *L_off, *rmap_off;
+    const double* L;
+};
+MfView mf_view(const MfDevice* d);
+struct SelInv;
+SelInv** mf_selinv_slot(MfDevice* d);
 // Test hook (bos_debug_inject_stall): the next factor flow launch starts at ticket 1, so its first
 // front is never processed and its parent's wait times out — the stall path, end to end.
 hipError_t mf_debug_skip_next_front(MfDevice* d, hipStream_t s);

@@ -34,6 +34,7 @@
 #include "../host/plan.hpp"
 #include "kernels.hpp"
 #include "multifrontal.hpp"
+#include "selinv.hpp"
 
 namespace {
 
@@ -199,6 +200,8 @@ struct bos_solver {
     // one GPU: the status sequence number last seen, and the status launches enqueued since (each
     // bumps the device counter once; wait_status polls for seq_seen + seq_pending)
     int32_t seq_seen = 0, seq_pending = 0;
+    // the last bos_marginals: J+H, factorization, selected inverse (events), download (host clock)
+    double marg_ms[4] = {};
 };
 
 static_assert(bos::dev::kStepAbort == bos::dev::kMfStall, "solver abort bit");
@@ -1938,6 +1941,60 @@ int bos_last_step_stamps(const bos_solver* s, uint64_t stamps[8]) {
     bos::dev::StepStatus h;
     std::memcpy(&h, (const void*)s->h_status, sizeof(h));   // the last step's summary (host-mapped)
     for (int i = 0; i < 8; ++i) stamps[i] = h.stamp[i];
+    return BOS_OK;
+}
+
+int bos_marginals(bos_solver* s, double* pose_cov, double* landmark_cov, int32_t* solver_info) {
+    if (!s) return fail(BOS_ERR_INVALID, "null handle");
+    if (!uses_mf(s))
+        return fail(BOS_ERR_UNSUPPORTED, "bos_marginals needs a multifrontal solver (BOS_SOLVER_SCHUR or BOS_SOLVER_SUPERNODAL)");
+    if (s->sharded || s->obs || s->world > 1 || s->comm || s->external || s->p2p)
+        return fail(BOS_ERR_UNSUPPORTED, "bos_marginals on a sharded handle (a rank holds part of the factor)");
+    HIP_TRY(hipSetDevice(s->device));
+    if (solver_info) *solver_info = 0;
+    const int64_t n = s->plan.n;
+    const size_t np9 = 9 * (size_t)s->NP, nl4 = 4 * (size_t)s->NL;
+    if (n == 0) {
+        if (pose_cov) std::fill(pose_cov, pose_cov + np9, 0.0);
+        if (landmark_cov) std::fill(landmark_cov, landmark_cov + nl4, 0.0);
+        return BOS_OK;
+    }
+    // bos_step returns on its status word, before the stream has drained: everything below is
+    // ordered after it by the stream
+    int rc;
+    HIP_TRY(hipEventRecord(s->ev[0], s->stream));
+    if ((rc = enqueue_linearize(s))) return rc;
+    HIP_TRY(hipEventRecord(s->ev[1], s->stream));
+    if ((rc = enqueue_solver_inputs(s))) return rc;   // opens the flows' epoch, as a step does
+    HIP_TRY(bos::dev::mf_factor(s->mf, 0, mf_matrix(s), s->d_rhs, s->stream));
+    s->have_dx = false;   // d_rhs now holds L^-1 b of this factorization
+    HIP_TRY(hipEventRecord(s->ev[2], s->stream));
+    const double* out = nullptr;
+    std::string err;
+    const int src = bos::dev::mf_selected_inverse(s->mf, s->plan, &out, s->stream, err);
+    // the factorization's word, read and cleared whatever happened next: a step expects it zero
+    int32_t info = 0;
+    hipError_t e = hipEventRecord(s->ev[3], s->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(&info, bos::dev::mf_info_ptr(s->mf), sizeof(info), hipMemcpyDeviceToHost, s->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(bos::dev::mf_info_ptr(s->mf), 0, sizeof(int32_t), s->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
+    HIP_TRY(e);
+    if (src) return fail(src == -1 ? BOS_ERR_UNSUPPORTED : BOS_ERR_DEVICE, err);
+    if (info & bos::dev::kMfStall)
+        return fail(BOS_ERR_SOLVER, "sparse factorization aborted: a dataflow dependency wait timed out");
+    const auto t0 = std::chrono::steady_clock::now();
+    if (pose_cov) HIP_TRY(hipMemcpy(pose_cov, out, np9 * sizeof(double), hipMemcpyDeviceToHost));
+    if (landmark_cov && nl4) HIP_TRY(hipMemcpy(landmark_cov, out + np9, nl4 * sizeof(double), hipMemcpyDeviceToHost));
+    s->marg_ms[3] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    for (int i = 0; i < 3; ++i) s->marg_ms[i] = elapsed(s->ev[i], s->ev[i + 1]);
+    if (solver_info) *solver_info = info;
+    return BOS_OK;
+}
+
+int bos_marginals_timing(const bos_solver* s, double ms[4], int64_t* sigma_bytes) {
+    if (!s || !ms) return fail(BOS_ERR_INVALID, "null argument");
+    for (int i = 0; i < 4; ++i) ms[i] = s->marg_ms[i];
+    if (sigma_bytes) *sigma_bytes = s->mf ? bos::dev::mf_selinv_sigma_bytes(s->mf) : 0;
     return BOS_OK;
 }
 

@@ -386,6 +386,31 @@ int bos_plan_mf_selftest(const bos_problem* pb, const bos_options* options, cons
     return BOS_OK;
 }
 
+// Test hook: the selected inverse (HostMf::selected_inverse) of the host factorization of H_nf given
+// by vals (bos_plan_inspect's order): the marginal covariance block of every node.
+int bos_plan_mf_marginals(const bos_problem* pb, const bos_options* options, const double* vals, double* pose_cov,
+                          double* landmark_cov) {
+    if (!pb || !vals || !pose_cov || (!landmark_cov && pb->num_landmarks > 0)) return hfail(BOS_ERR_INVALID, "null argument");
+    bos::ProblemIndex pi;
+    bos_options opt;
+    int fmode = 0;
+    int rc = plan_args(pb, options, pi, fmode, opt);
+    if (rc) return rc;
+    if (opt.solver != BOS_SOLVER_SUPERNODAL && opt.solver != BOS_SOLVER_SCHUR)
+        return hfail(BOS_ERR_INVALID, "marginals need a multifrontal solver");
+    bos::Plan P;
+    std::string err;
+    rc = bos::build_plan(pi, 0, 1, fmode, P, err);
+    if (rc) return hfail(rc, err);
+    const std::vector<double> rhs(P.n, 0.0);
+    bos::HostMf M(P, vals, rhs.data());
+    M.factor([](int) { return true; });
+    double none = 0.0;
+    if (!M.selected_inverse(pose_cov, landmark_cov ? landmark_cov : &none))
+        return hfail(BOS_ERR_INVALID, "a node's dofs are split between two supernodes");
+    return BOS_OK;
+}
+
 // The sharded solve (plan.hpp Shard) simulated on the host for all `world` ranks, exchanges
 // included (the all-gathers become concatenations of the per-rank send buffers). Every rank builds
 // its own plan, holds only the block values its J+H computes (vals scattered through its

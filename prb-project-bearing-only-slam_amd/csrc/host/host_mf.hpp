@@ -242,6 +242,92 @@ struct HostMf {
         else
             for (int s : folds) backward_front(s);
     }
+
+    // ---- selected inverse (Takahashi recursion): the diagonal blocks of (P^T H_nf P)^-1 from the
+    // finished L panels, top-down over the assembly tree. sig holds the Sigma front (full m x m
+    // column-major, [[S_JJ, .], [S_RJ, G]]) of every supernode that has children (folded ones count).
+    std::vector<std::vector<double>> sig;
+
+    void selinv_front(int s, double* pose_cov, double* lm_cov, const std::vector<int32_t>& out_ptr,
+                      const std::vector<int32_t>& out_rec) {
+        const int k = F.k[s], r = F.r[s], m = k + r, p = F.parent[s];
+        const double* Ls = L.data() + F.L_off[s];
+        // G = Sigma_RR from the parent's front through rmap
+        std::vector<double> G((size_t)r * r);
+        if (r > 0) {
+            const int mp = F.k[p] + F.r[p];
+            const double* Sp = sig[p].data();
+            const int32_t* map = F.rmap.data() + F.rmap_off[s];
+            for (int j = 0; j < r; ++j)
+                for (int i = 0; i < r; ++i) G[i + (size_t)j * r] = Sp[map[i] + (size_t)map[j] * mp];
+        }
+        // Li = L11^-1 (lower triangle of L11 only), column by column
+        std::vector<double> Li((size_t)k * k, 0.0);
+        for (int j = 0; j < k; ++j)
+            for (int i = j; i < k; ++i) {
+                double acc = i == j ? 1.0 : 0.0;
+                for (int l = j; l < i; ++l) acc -= Ls[i + (size_t)l * m] * Li[l + (size_t)j * k];
+                Li[i + (size_t)j * k] = acc / Ls[i + (size_t)i * m];
+            }
+        // Z = L21 L11^-1, S_RJ = -G Z
+        std::vector<double> Z((size_t)r * k), S((size_t)r * k);
+        for (int j = 0; j < k; ++j)
+            for (int i = 0; i < r; ++i) {
+                double acc = 0.0;
+                for (int l = j; l < k; ++l) acc += Ls[(k + i) + (size_t)l * m] * Li[l + (size_t)j * k];
+                Z[i + (size_t)j * r] = acc;
+            }
+        for (int j = 0; j < k; ++j)
+            for (int i = 0; i < r; ++i) {
+                double acc = 0.0;
+                for (int l = 0; l < r; ++l) acc += G[i + (size_t)l * r] * Z[l + (size_t)j * r];
+                S[i + (size_t)j * r] = -acc;
+            }
+        // S_JJ = L11^-T L11^-1 - Z^T S_RJ: the lower triangle, mirrored
+        std::vector<double> J((size_t)k * k);
+        for (int b = 0; b < k; ++b)
+            for (int a = b; a < k; ++a) {
+                double acc = 0.0;
+                for (int l = a; l < k; ++l) acc += Li[l + (size_t)a * k] * Li[l + (size_t)b * k];
+                for (int i = 0; i < r; ++i) acc -= Z[i + (size_t)a * r] * S[i + (size_t)b * r];
+                J[a + (size_t)b * k] = J[b + (size_t)a * k] = acc;
+            }
+        if (F.child_ptr[s + 1] > F.child_ptr[s]) {
+            std::vector<double>& Sf = sig[s];
+            Sf.assign((size_t)m * m, 0.0);
+            for (int b = 0; b < k; ++b)
+                for (int a = 0; a < k; ++a) Sf[a + (size_t)b * m] = J[a + (size_t)b * k];
+            for (int j = 0; j < k; ++j)
+                for (int i = 0; i < r; ++i) Sf[(k + i) + (size_t)j * m] = Sf[j + (size_t)(k + i) * m] = S[i + (size_t)j * r];
+            for (int j = 0; j < r; ++j)
+                for (int i = 0; i < r; ++i) Sf[(k + i) + (size_t)(k + j) * m] = G[i + (size_t)j * r];
+        }
+        for (int q = out_ptr[s]; q < out_ptr[s + 1]; ++q) {   // whole nodes of this supernode
+            const int loc = out_rec[3 * q], dst = out_rec[3 * q + 1], sz = out_rec[3 * q + 2];
+            double* o = sz == 3 ? pose_cov + dst : lm_cov + dst;
+            for (int a = 0; a < sz; ++a)
+                for (int b = 0; b < sz; ++b) o[a * sz + b] = J[(loc + a) + (size_t)(loc + b) * k];
+        }
+    }
+
+    // pose_cov [NP * 9], lm_cov [NL * 4] (row-major, stix order; the fixed pose's block zero); L holds
+    // the factor (factor() has run). Returns false when a node straddles two supernodes.
+    bool selected_inverse(double* pose_cov, double* lm_cov) {
+        std::vector<int32_t> out_ptr, out_rec;
+        if (!selinv_records(P, out_ptr, out_rec)) return false;
+        std::fill(pose_cov, pose_cov + 9 * (size_t)P.NP, 0.0);
+        std::fill(lm_cov, lm_cov + 4 * (size_t)P.NL, 0.0);
+        sig.assign(F.nsuper, {});
+        auto all = [](int) { return true; };
+        each_level(true, all, [&](int s) { selinv_front(s, pose_cov, lm_cov, out_ptr, out_rec); });
+        const std::vector<int32_t>& folds = F.fold_list;
+        auto body = [&](int64_t j) { selinv_front(folds[j], pose_cov, lm_cov, out_ptr, out_rec); };
+        if (pool) pool->parallel_for((int64_t)folds.size(), body);
+        else
+            for (size_t j = 0; j < folds.size(); ++j) body((int64_t)j);
+        sig.clear();
+        return true;
+    }
 };
 
 }  // namespace bos

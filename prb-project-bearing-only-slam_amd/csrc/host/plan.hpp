@@ -241,6 +241,36 @@ struct Plan {
     int64_t nnzL() const { return Lptr.empty() ? 0 : Lptr.back(); }
 };
 
+// Selected inverse (HostMf::selected_inverse, hip/selinv.hip): the whole nodes of every supernode.
+// Records out_rec[3 q ...] = (the node's first dof inside the supernode's k own dofs, its block's
+// offset in the output: 9 u for pose u in pose_cov, 4 l for landmark l in landmark_cov, its dofs: 3 or
+// 2) for q in [out_ptr[s], out_ptr[s + 1]). False when a node's dofs are not inside one supernode.
+inline bool selinv_records(const Plan& P, std::vector<int32_t>& out_ptr, std::vector<int32_t>& out_rec) {
+    const Multifrontal& F = P.mf;
+    std::vector<int32_t> sn_of(P.n, -1), cnt(F.nsuper + 1, 0);
+    for (int s = 0; s < F.nsuper; ++s)
+        for (int i = 0; i < F.k[s]; ++i) sn_of[F.col0[s] + i] = s;
+    const int nodes = P.NP + P.NL;
+    for (int u = 0; u < nodes; ++u) {
+        if (u == P.fixed) continue;
+        const int sz = u < P.NP ? 3 : 2, d = P.node_dof[u];
+        if (d < 0 || d + sz > P.n || sn_of[d] < 0 || sn_of[d + sz - 1] != sn_of[d]) return false;
+        ++cnt[sn_of[d] + 1];
+    }
+    out_ptr.assign(F.nsuper + 1, 0);
+    for (int s = 0; s < F.nsuper; ++s) out_ptr[s + 1] = out_ptr[s] + cnt[s + 1];
+    out_rec.assign(3 * (size_t)out_ptr[F.nsuper], 0);
+    std::vector<int32_t> fill(out_ptr.begin(), out_ptr.end() - 1);
+    for (int u = 0; u < nodes; ++u) {
+        if (u == P.fixed) continue;
+        const int d = P.node_dof[u], s = sn_of[d], q = fill[s]++;
+        out_rec[3 * q] = d - F.col0[s];
+        out_rec[3 * q + 1] = u < P.NP ? 9 * u : 4 * (u - P.NP);
+        out_rec[3 * q + 2] = u < P.NP ? 3 : 2;
+    }
+    return true;
+}
+
 enum FactorMode {
     kFactorNone = 0,          // dense solver: pattern only
     kFactorScalar = 1,        // scalar CSR Cholesky pattern (rocSOLVER csrrf), cheapest-flops ordering
