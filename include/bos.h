@@ -274,6 +274,57 @@ int bos_get_last_dx(const struct bos_solver* s, double* dx);
  * handles (world_size > 1, a communicator, or external / direct exchange); BOS_ERR_DEVICE (with the
  * byte count in bos_last_error) when the pass's buffers cannot be allocated: the handle stays usable. */
 int bos_marginals(struct bos_solver* s, double* pose_cov, double* landmark_cov, int32_t* solver_info);
+/*
+ * Levenberg-Marquardt with on-device step control (DESIGN.md §4 "Levenberg-Marquardt"). The objective is
+ *   F(x) = sum over all edges of h(rho), rho = e^T Omega e, h(rho) = rho for rho <= kt and
+ *   2 sqrt(kt rho) - kt beyond (Huber in squared form): the function whose half gradient the robust
+ *   J+H build computes; with a kernel threshold past every rho it is the chi2 of bos_step_stats.
+ * One iteration at state x with damping lambda: H = H0 + lambda I and b built at x (an iteration with
+ * lambda = d is the linear system of a bos_step with damping factor d), H x_s = b solved (dx = -x_s),
+ * predicted = dx^T (lambda dx - b), trial state x [+] dx, gain = (F - F') / predicted. The step is
+ * accepted iff the factorization met no non-positive pivot, predicted > 0, F' is finite and gain > 0:
+ * then lambda <- lambda max(1/3, 1 - (2 gain - 1)^3), nu <- 2; otherwise the state is rolled back,
+ * lambda <- lambda nu, nu <- 2 nu. lambda stays in [lambda_min, lambda_max]. Stop tests, in this
+ * order: 1 max |dx| <= dx_tol (an accepted step is kept, a rejected one is not), 2 accepted and
+ * F - F' <= f_tol F, 4 rejected with lambda already at lambda_max, 3 max_iterations reached.
+ * lambda, the gain, the decision and the rollback are device code: check_every iterations are
+ * enqueued between two host reads of the status; after a stop the remaining iterations of a batch
+ * change nothing (rejected, not counted).
+ */
+typedef struct bos_lm_options {
+    double lambda0;        /* > 0: restart with this lambda and nu = 2; 0: continue from the handle's
+                              last lambda/nu (first call: the handle's damping factor) */
+    double lambda_min, lambda_max;   /* defaults 1e-12, 1e12 */
+    double dx_tol, f_tol;            /* defaults 1e-6, 1e-12; 0 disables a test */
+    int32_t max_iterations;          /* default 50; 1 .. 4096 */
+    int32_t check_every;             /* iterations enqueued between host reads of the status, default 4 */
+} bos_lm_options;
+typedef struct bos_lm_iteration { double cost, cost_trial, predicted, gain, lambda, max_abs_dx;
+                                  int32_t solver_info, accepted; } bos_lm_iteration;
+typedef struct bos_lm_result { int32_t iterations, accepted, rejected, reason;
+                               double cost_initial, cost_final, lambda_final; } bos_lm_result;
+void bos_lm_default_options(bos_lm_options* opt);
+/* F, the plain chi2 and the count of edges with rho > kt at the handle's current state and kernel
+ * threshold; any output may be NULL. Evaluated in fp64 from the master state on every handle (fp32
+ * ones included); no H is built, the last linearization stays as it is. Synchronous. Any one-GPU
+ * handle (every solver); BOS_ERR_UNSUPPORTED on sharded handles. */
+int bos_cost(struct bos_solver* s, double* cost, double* chi2, int32_t* n_robust);
+/* Runs LM iterations until a stop test fires (result->reason, 1-4 above; options NULL: the
+ * defaults). Synchronous. On return the state is the last accepted iterate. trace (may be NULL)
+ * receives one record per counted iteration, the first min(iterations, trace_capacity) of them.
+ * Afterwards bos_export_system gives the damped system of the last iteration that ran on the device
+ * (the last counted one unless a batch went on past a stop: those re-linearise at the final state),
+ * bos_get_last_dx returns BOS_ERR_INVALID until the next bos_step, and a following bos_step behaves
+ * as if the state had been set with bos_set_state (its T caches are the box-plus kernel's, as after
+ * a bos_step: on an fp32 handle their cos / sin can differ from bos_set_state's host-computed ones
+ * by an ulp of fp32). The kernel threshold is the handle's; its damping
+ * factor is not changed. A stalled factorization returns BOS_ERR_SOLVER with the state at the last
+ * accepted iterate. BOS_ERR_UNSUPPORTED on BOS_SOLVER_DENSE_CHOL / BOS_SOLVER_ROCSOLVER_RF handles
+ * and on sharded handles; BOS_ERR_DEVICE when the feature's buffers cannot be allocated: the handle
+ * stays usable. */
+int bos_optimize(struct bos_solver* s, const bos_lm_options* options, bos_lm_result* result,
+                 bos_lm_iteration* trace, int32_t trace_capacity);
+
 /* Diagnostics: the phase boundaries of the last completed step, realtime clock (100 MHz ticks),
  * as the step's own kernels stamped them: [0] J+H start, [1] J+H end / solve start, [2] solve end,
  * [3] step end; subtree-sharded handles: [4] phase 0 done (own subtrees factored, exchange 1

@@ -55,7 +55,13 @@ EXPORTED_SYMBOLS = [
     "bos_cpu_gn_destroy", "bos_normalized_angle_f64", "bos_normalized_angle_f32", "bos_exchange_p2p_handle",
     "bos_exchange_p2p_connect", "bos_time_facade_steps", "bos_debug_facade_selftest", "bos_set_exchange_timeout",
     "bos_last_step_stamps", "bos_marginals", "bos_plan_mf_marginals", "bos_marginals_timing",
+    "bos_lm_default_options", "bos_cost", "bos_optimize", "bos_time_cost", "bos_cpu_gn_set_kernel_threshold",
+    "bos_cpu_gn_cost", "bos_cpu_gn_optimize", "bos_lm_rule_apply",
 ]
+
+# bos_lm_result.reason
+LM_STOP_DX, LM_STOP_COST, LM_STOP_ITERATIONS, LM_STOP_LAMBDA = 1, 2, 3, 4
+LM_MAX_ITERATIONS = 4096
 
 P2P_HANDLE_BYTES = 64   # include/bos.h BOS_P2P_HANDLE_BYTES
 
@@ -98,6 +104,36 @@ class bos_system_info(ctypes.Structure):
                 ("landmark_lanes", ctypes.c_int32), ("own_fronts", ctypes.c_int32), ("top_fronts", ctypes.c_int32),
                 ("comm_ranks", ctypes.c_int32), ("partition", ctypes.c_int32),
                 ("pl_factored", ctypes.c_int32), ("fold_fp32", ctypes.c_int32), ("layout_bytes", ctypes.c_int64)]
+
+
+class bos_lm_options(ctypes.Structure):
+    _fields_ = [("lambda0", ctypes.c_double), ("lambda_min", ctypes.c_double), ("lambda_max", ctypes.c_double),
+                ("dx_tol", ctypes.c_double), ("f_tol", ctypes.c_double), ("max_iterations", ctypes.c_int32),
+                ("check_every", ctypes.c_int32)]
+
+
+class bos_lm_iteration(ctypes.Structure):
+    _fields_ = [("cost", ctypes.c_double), ("cost_trial", ctypes.c_double), ("predicted", ctypes.c_double),
+                ("gain", ctypes.c_double), ("lambda", ctypes.c_double), ("max_abs_dx", ctypes.c_double),
+                ("solver_info", ctypes.c_int32), ("accepted", ctypes.c_int32)]
+
+
+class bos_lm_result(ctypes.Structure):
+    _fields_ = [("iterations", ctypes.c_int32), ("accepted", ctypes.c_int32), ("rejected", ctypes.c_int32),
+                ("reason", ctypes.c_int32), ("cost_initial", ctypes.c_double), ("cost_final", ctypes.c_double),
+                ("lambda_final", ctypes.c_double)]
+
+
+class bos_lm_state(ctypes.Structure):
+    _fields_ = [("lambda", ctypes.c_double), ("nu", ctypes.c_double), ("cost", ctypes.c_double),
+                ("iteration", ctypes.c_int32), ("accepted", ctypes.c_int32), ("rejected", ctypes.c_int32),
+                ("done", ctypes.c_int32), ("reason", ctypes.c_int32)]
+
+
+# one record of an optimize() trace (bos_lm_iteration)
+LM_TRACE_DTYPE = np.dtype([("cost", "f8"), ("cost_trial", "f8"), ("predicted", "f8"), ("gain", "f8"), ("lambda", "f8"),
+                           ("max_abs_dx", "f8"), ("solver_info", "i4"), ("accepted", "i4")])
+assert LM_TRACE_DTYPE.itemsize == ctypes.sizeof(bos_lm_iteration)
 
 
 class bos_plan_info(ctypes.Structure):
@@ -171,6 +207,18 @@ def lib():
         "bos_plan_mf_marginals": (ctypes.c_int, [ctypes.POINTER(bos_problem), ctypes.POINTER(bos_options), _dp, _dp, _dp]),
         "bos_marginals": (ctypes.c_int, [vp, _dp, _dp, _ip]),
         "bos_marginals_timing": (ctypes.c_int, [vp, _dp, ctypes.POINTER(ctypes.c_int64)]),
+        "bos_lm_default_options": (None, [ctypes.POINTER(bos_lm_options)]),
+        "bos_cost": (ctypes.c_int, [vp, _dp, _dp, _ip]),
+        "bos_optimize": (ctypes.c_int, [vp, ctypes.POINTER(bos_lm_options), ctypes.POINTER(bos_lm_result),
+                                        ctypes.POINTER(bos_lm_iteration), ctypes.c_int32]),
+        "bos_time_cost": (ctypes.c_int, [vp, ctypes.c_int32, _dp]),
+        "bos_cpu_gn_set_kernel_threshold": (ctypes.c_int, [vp, ctypes.c_double]),
+        "bos_cpu_gn_cost": (ctypes.c_int, [vp, _dp, _dp, _ip]),
+        "bos_cpu_gn_optimize": (ctypes.c_int, [vp, ctypes.POINTER(bos_lm_options), ctypes.POINTER(bos_lm_result),
+                                               ctypes.POINTER(bos_lm_iteration), ctypes.c_int32]),
+        "bos_lm_rule_apply": (ctypes.c_int, [ctypes.POINTER(bos_lm_state), ctypes.POINTER(bos_lm_options), ctypes.c_double,
+                                             ctypes.c_double, ctypes.c_double, ctypes.c_int32,
+                                             ctypes.POINTER(bos_lm_iteration)]),
         "bos_plan_shard_selftest": (ctypes.c_int, [ctypes.POINTER(bos_problem), ctypes.POINTER(bos_options), ctypes.c_int32,
                                                    _dp, _dp, _dp]),
         "bos_plan_node_owner": (ctypes.c_int, [ctypes.POINTER(bos_problem), ctypes.POINTER(bos_options), ctypes.c_int32, _ip]),
@@ -465,6 +513,52 @@ def plan_node_owner(P: Problem, world: int, solver: int = BOS_SOLVER_SCHUR) -> n
     return o
 
 
+def lm_options(**opts) -> bos_lm_options:
+    """bos_lm_options: the defaults (bos_lm_default_options) with the given fields replaced."""
+    o = bos_lm_options()
+    lib().bos_lm_default_options(ctypes.byref(o))
+    names = {k for k, _ in bos_lm_options._fields_}
+    for k, v in opts.items():
+        if k not in names:
+            raise TypeError(f"unknown LM option {k!r}")
+        setattr(o, k, v)
+    return o
+
+
+def lm_rule_apply(state: dict, opts: bos_lm_options, cost_trial: float, predicted: float, max_abs_dx: float,
+                  solver_info: int = 0):
+    """One decision of the LM step control (bos_lm_rule_apply, the code the device and the CPU twin
+    run): (new state dict, record dict, counted)."""
+    st = bos_lm_state()
+    for k, _ in bos_lm_state._fields_:
+        setattr(st, k, state.get(k, 0))
+    rec = bos_lm_iteration()
+    rc = lib().bos_lm_rule_apply(ctypes.byref(st), ctypes.byref(opts), cost_trial, predicted, max_abs_dx, solver_info,
+                                 ctypes.byref(rec))
+    if rc < 0:
+        _check(rc, "bos_lm_rule_apply")
+    return ({k: getattr(st, k) for k, _ in bos_lm_state._fields_},
+            {k: getattr(rec, k) for k, _ in bos_lm_iteration._fields_}, bool(rc))
+
+
+def _run_optimize(fn, h, what, opts) -> dict:
+    o = lm_options(**opts)
+    cap = max(1, min(int(o.max_iterations), LM_MAX_ITERATIONS))
+    trace = np.zeros(cap, dtype=LM_TRACE_DTYPE)
+    res = bos_lm_result()
+    _check(fn(h, ctypes.byref(o), ctypes.byref(res), trace.ctypes.data_as(ctypes.POINTER(bos_lm_iteration)), cap), what)
+    out = {k: getattr(res, k) for k, _ in bos_lm_result._fields_}
+    out["trace"] = trace[:res.iterations].copy()
+    return out
+
+
+def _run_cost(fn, h, what) -> dict:
+    F, chi = ctypes.c_double(0), ctypes.c_double(0)
+    nrob = ctypes.c_int32(0)
+    _check(fn(h, ctypes.byref(F), ctypes.byref(chi), ctypes.byref(nrob)), what)
+    return {"cost": F.value, "chi2": chi.value, "n_robust": nrob.value}
+
+
 class CpuGN:
     """The CPU baseline of bench.py (include/bos_host.h bos_cpu_gn_*): the same GN iteration on the
     host's cores with the build's own host multifrontal Cholesky. Not a fallback of Solver."""
@@ -479,6 +573,17 @@ class CpuGN:
         c = ctypes.c_double(0)
         _check(lib().bos_cpu_gn_step(self._h, ctypes.byref(c)), "bos_cpu_gn_step")
         return c.value
+
+    def set_kernel_threshold(self, kt: float):
+        _check(lib().bos_cpu_gn_set_kernel_threshold(self._h, kt), "bos_cpu_gn_set_kernel_threshold")
+
+    def cost(self) -> dict:
+        """The objective at the current state (bos_cpu_gn_cost): cost, chi2, n_robust."""
+        return _run_cost(lib().bos_cpu_gn_cost, self._h, "bos_cpu_gn_cost")
+
+    def optimize(self, **opts) -> dict:
+        """The CPU twin of Solver.optimize (bos_cpu_gn_optimize): same options, result and trace."""
+        return _run_optimize(lib().bos_cpu_gn_optimize, self._h, "bos_cpu_gn_optimize", opts)
 
     def get_state(self):
         pose = np.zeros((self.P.NP, 3))
@@ -710,6 +815,23 @@ class Solver:
         _check(lib().bos_marginals(self._h, _ptr(pose, ctypes.c_double), _ptr(lm, ctypes.c_double),
                                    ctypes.byref(info)), "bos_marginals")
         return pose, lm, info.value
+
+    def cost(self) -> dict:
+        """The objective F at the current state, the plain chi2 and the count of edges beyond the
+        kernel threshold (bos_cost; fp64 on every handle, no H is built)."""
+        return _run_cost(lib().bos_cost, self._h, "bos_cost")
+
+    def optimize(self, **opts) -> dict:
+        """Levenberg-Marquardt with on-device step control (bos_optimize). opts: the fields of
+        bos_lm_options (lambda0, lambda_min, lambda_max, dx_tol, f_tol, max_iterations, check_every).
+        Returns the bos_lm_result fields plus "trace": one LM_TRACE_DTYPE record per iteration."""
+        return _run_optimize(lib().bos_optimize, self._h, "bos_optimize", opts)
+
+    def time_cost(self, n: int) -> float:
+        """ms per launch of the cost kernel (HIP events, bos_time_cost)."""
+        ms = ctypes.c_double(0)
+        _check(lib().bos_time_cost(self._h, n, ctypes.byref(ms)), "bos_time_cost")
+        return ms.value
 
     def marginals_timing(self) -> dict:
         """The last marginals() call's split in ms and the Sigma-front buffer's bytes (bos_marginals_timing)."""

@@ -1,6 +1,8 @@
 // Headless drop-in for executables/bearing_only_slam.cpp (reference :40-116).
-// Usage: bearing_only_slam <dataset_fname> [--iters N] [--fp32] [--dense|--schur] [--dump out.g2o]
+// Usage: bearing_only_slam <dataset_fname> [--iters N] [--lm] [--fp32] [--dense|--schur] [--dump out.g2o]
 //                          [--ppm out.ppm] [--quiet]
+// --lm: Levenberg-Marquardt (bos_optimize, at most --iters iterations, it stops by itself) instead of
+// the fixed count of Gauss-Newton steps; one line per iteration.
 // Same flow as the reference's main: parse_g2o, default the fixed pose, triangulate the
 // landmarks, construct the Solver, then iterate (the reference's Tab press = 50 iterations,
 // :93-99). The OpenCV window is replaced by a per-iteration chi^2 line, an optional g2o dump and
@@ -9,7 +11,9 @@
 #include <cstdlib>
 #include <cstring>
 #include <iostream>
+#include <stdexcept>
 #include <string>
+#include <vector>
 
 #include "../host/draw_ppm.hpp"
 #include "../host/g2o_utils.hpp"
@@ -20,18 +24,19 @@ using namespace proj02;
 
 int main(int argc, char** argv) {
     if (argc < 2) {
-        std::cout << "usage: bearing_only_slam <dataset_fname> [--iters N] [--fp32] [--dense|--schur] [--dump out.g2o] "
+        std::cout << "usage: bearing_only_slam <dataset_fname> [--iters N] [--lm] [--fp32] [--dense|--schur] [--dump out.g2o] "
                      "[--ppm out.ppm] [--quiet]"
                   << std::endl;
         return 1;
     }
     int iters = 50;
-    bool quiet = false;
+    bool quiet = false, lm = false;
     std::string dump, ppm;
     bos_options opt;
     bos_default_options(&opt);
     for (int i = 2; i < argc; ++i) {
         if (!std::strcmp(argv[i], "--iters") && i + 1 < argc) iters = std::atoi(argv[++i]);
+        else if (!std::strcmp(argv[i], "--lm")) lm = true;
         else if (!std::strcmp(argv[i], "--fp32")) opt.precision = BOS_FP32;
         else if (!std::strcmp(argv[i], "--dense")) opt.solver = BOS_SOLVER_DENSE_CHOL;
         else if (!std::strcmp(argv[i], "--schur")) opt.solver = BOS_SOLVER_SCHUR;
@@ -59,7 +64,25 @@ int main(int argc, char** argv) {
     if (!ppm.empty()) render(state, ppm.substr(0, ppm.rfind('.')) + "_initial.ppm");
     try {
         Solver solver(state, bearings, odometries, fixed_pose_id, &opt);
-        for (int it = 0; it < iters; ++it) {
+        if (lm) {
+            bos_lm_options lo;
+            bos_lm_default_options(&lo);
+            lo.max_iterations = iters;
+            std::vector<bos_lm_iteration> trace(iters > 0 ? iters : 0);
+            bos_lm_result res;
+            if (bos_optimize(solver.handle(), &lo, &res, trace.data(), (int32_t)trace.size()) != BOS_OK)
+                throw std::runtime_error(bos_last_error());
+            if (!quiet) {
+                for (int it = 0; it < res.iterations; ++it) {
+                    const bos_lm_iteration& r = trace[it];
+                    std::printf("iter %3d  cost %.9g  trial %.9g  gain %.3g  lambda %.3g  max|dx| %.3g  %s\n", it, r.cost,
+                                r.cost_trial, r.gain, r.lambda, r.max_abs_dx, r.accepted ? "accepted" : "rejected");
+                }
+                std::printf("stopped after %d iterations (%d accepted, %d rejected), reason %d, cost %.9g -> %.9g\n",
+                            res.iterations, res.accepted, res.rejected, res.reason, res.cost_initial, res.cost_final);
+            }
+        }
+        for (int it = 0; it < iters && !lm; ++it) {
             solver.step();
             const bos_step_stats& s = solver.last_stats();
             if (!quiet)

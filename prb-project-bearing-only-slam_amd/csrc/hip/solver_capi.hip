@@ -33,6 +33,7 @@
 #include "../host/error.hpp"
 #include "../host/plan.hpp"
 #include "kernels.hpp"
+#include "lm.hpp"
 #include "multifrontal.hpp"
 #include "selinv.hpp"
 
@@ -202,7 +203,25 @@ struct bos_solver {
     int32_t seq_seen = 0, seq_pending = 0;
     // the last bos_marginals: J+H, factorization, selected inverse (events), download (host clock)
     double marg_ms[4] = {};
+    // ---- bos_cost / bos_optimize (hip/lm.hpp). The fp64 originals of what the cost pass reads and the
+    // J+H keeps only in T: odometry z / information (upper triangle) and the bearing weights (has_w)
+    std::vector<double> h_oz, h_oom, h_bw;
+    // device buffers, one allocation (lm_arena) made at the first use of either call
+    char* lm_arena = nullptr;
+    int32_t *lm_blm = nullptr, *lm_lane_lm = nullptr, *lm_pnrob = nullptr;
+    double *lm_bw = nullptr, *lm_oz = nullptr, *lm_oom = nullptr;
+    double *lm_pF = nullptr, *lm_pchi = nullptr, *lm_pxx = nullptr, *lm_pxb = nullptr;
+    uint32_t* lm_backup[5] = {};                 // d_pose, d_lm, d_pc, d_pth, d_lc before the trial box-plus
+    bos::dev::LmControl* lm_ctl = nullptr;       // the loop's state (device)
+    bos::dev::LmControl* lm_hctl = nullptr;      // its host-mapped copy, written by the decision kernel
+    bos::dev::LmControl* lm_mctl = nullptr;      // device address of lm_hctl
+    bos_lm_iteration* lm_trace = nullptr;        // [kLmTraceCap]
+    bool lm_started = false;                     // lm_lambda / lm_nu hold the last call's final values
+    double lm_lambda = 0.0, lm_nu = 2.0;
+    hipGraph_t lm_graph = nullptr;               // one LM iteration (multifrontal handles)
+    hipGraphExec_t lm_exec = nullptr;
 };
+constexpr int32_t kLmTraceCap = 4096;   // bos_lm_options.max_iterations' upper limit
 
 static_assert(bos::dev::kStepAbort == bos::dev::kMfStall, "solver abort bit");
 static_assert(bos::dev::kExHeader == bos::kExHeader, "exchange header size");
@@ -304,16 +323,19 @@ int flush_stage(bos_solver* s, JhStage& st) {
     return BOS_OK;
 }
 
-int enqueue_linearize(bos_solver* s, unsigned long long* t_start = nullptr) {
+// undamped: lambda 0 in the launch arguments (an LM iteration adds its own from device memory)
+int enqueue_linearize(bos_solver* s, unsigned long long* t_start = nullptr, bool undamped = false) {
     hipError_t e;
     const int lpp = s->plan.blk.lpp;
     if (s->precision == BOS_FP32) {
         bos::dev::LinParams<float> p = lin_params<float>(s);
         p.t_start = t_start;
+        if (undamped) p.lambda = 0.f;
         e = bos::dev::launch_linearize<float>(p, lpp, s->has_w, s->has_dups, s->stream);
     } else {
         bos::dev::LinParams<double> p = lin_params<double>(s);
         p.t_start = t_start;
+        if (undamped) p.lambda = 0.0;
         e = bos::dev::launch_linearize<double>(p, lpp, s->has_w, s->has_dups, s->stream);
     }
     if (e != hipSuccess) return fail(BOS_ERR_DEVICE, std::string("linearize launch: ") + hipGetErrorString(e));
@@ -702,6 +724,7 @@ int shard_enqueue(bos_solver* s, int phase, bool with_jh = true) {
 
 int capture(bos_solver* s, int phase, hipGraph_t* graph, hipGraphExec_t* exec);
 int enqueue_step_tail(bos_solver* s);
+int enqueue_lm_iteration(bos_solver* s);
 
 // ---- BOS_PARTITION_OBSERVATIONS step (the north star's form): phase 0 = this rank's range of J+H
 // lanes and its chi^2 / robust-count header (external mode: the whole [header | H values | b] in
@@ -962,10 +985,14 @@ void drop_graph(bos_solver* s) {
     if (s->stail) (void)hipGraphDestroy(s->stail);
     s->sexec = s->stail_exec = nullptr;
     s->sgraph = s->stail = nullptr;
+    if (s->lm_exec) (void)hipGraphExecDestroy(s->lm_exec);
+    if (s->lm_graph) (void)hipGraphDestroy(s->lm_graph);
+    s->lm_exec = nullptr;
+    s->lm_graph = nullptr;
 }
 
 // Capture the launches of one GN step (phase -1: the one-GPU step after its J+H build,
-// enqueue_step_tail; -2: the whole one-GPU step; 0-2: a subtree-sharded phase; 10-11: an
+// enqueue_step_tail; -2: the whole one-GPU step; -3: one LM iteration, enqueue_lm_iteration; 0-2: a subtree-sharded phase; 10-11: an
 // observations-partition phase) into *exec (multifrontal
 // solvers: rocSOLVER's paths are not captured). A stream that cannot be captured leaves
 // graph_failed set and the launches run eagerly, the same ones in the same order.
@@ -977,6 +1004,7 @@ int capture(bos_solver* s, int phase, hipGraph_t* graph, hipGraphExec_t* exec) {
     }
     const int rc = phase == -1   ? enqueue_step_tail(s)
                    : phase == -2 ? enqueue_step(s)
+                   : phase == -3 ? enqueue_lm_iteration(s)
                    : phase >= 10 ? obs_enqueue(s, phase - 10)
                                  : shard_enqueue(s, phase);
     hipGraph_t g = nullptr;
@@ -1056,6 +1084,182 @@ int scrub_caches(bos_solver* s) {
     return BOS_OK;
 }
 
+// ---- bos_cost / bos_optimize (hip/lm.hpp)
+
+bool lm_sharded(const bos_solver* s) {
+    return s->sharded || s->obs || s->world > 1 || s->comm || s->external || s->p2p;
+}
+
+// word counts of the five state arrays the trial box-plus writes (d_pose, d_lm, d_pc, d_pth, d_lc)
+void lm_state_words(const bos_solver* s, int64_t w[5]) {
+    const int64_t tw = (int64_t)s->tsize / 4;
+    w[0] = 6 * (int64_t)s->NP;
+    w[1] = 4 * (int64_t)s->NL;
+    w[2] = 4 * (int64_t)s->NP * tw;
+    w[3] = (int64_t)s->NP * tw;
+    w[4] = 2 * (int64_t)s->NL * tw;
+}
+
+// The feature's buffers, at its first use: the fp64 observations of the cost pass, the partials, the
+// state backup, the control block and the trace in one allocation, and the control block's host-mapped
+// copy. A failure frees what was made and leaves the handle as it was.
+int lm_setup(bos_solver* s) {
+    if (s->lm_arena) return BOS_OK;
+    const bos::Plan& P = s->plan;
+    // landmark of every bearing, measurement order, from the triangulation's CSR (by landmark)
+    std::vector<int32_t> blm(s->Mb, 0);
+    if (s->Mb) {
+        std::vector<int32_t> tptr(s->NL + 1), tobs(s->Mb);
+        HIP_TRY(hipMemcpy(tptr.data(), s->tri_ptr, tptr.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(tobs.data(), s->tri_obs, tobs.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+        for (int l = 0; l < s->NL; ++l)
+            for (int q = tptr[l]; q < tptr[l + 1]; ++q) blm[tobs[q]] = l;
+    }
+    JhStage st;
+    int64_t w[5];
+    lm_state_words(s, w);
+    const size_t nc = (size_t)std::max(1, bos::dev::lm_cost_parts(s->Mb, s->Mo));
+    const size_t nm = (size_t)std::max(1, bos::dev::lm_model_parts(P.n));
+    void* ctl = nullptr;
+    void* trace = nullptr;
+    st.add(&s->lm_blm, blm);
+    st.add(&s->lm_lane_lm, P.blk.lm_lane_lm);
+    st.add(&s->lm_bw, s->h_bw);
+    st.add(&s->lm_oz, s->h_oz);
+    st.add(&s->lm_oom, s->h_oom);
+    st.add(&s->lm_pF, std::vector<double>(nc, 0.0));
+    st.add(&s->lm_pchi, std::vector<double>(nc, 0.0));
+    st.add(&s->lm_pnrob, std::vector<int32_t>(nc, 0));
+    st.add(&s->lm_pxx, std::vector<double>(nm, 0.0));
+    st.add(&s->lm_pxb, std::vector<double>(nm, 0.0));
+    for (int a = 0; a < 5; ++a) st.add(&s->lm_backup[a], std::vector<uint32_t>((size_t)w[a], 0u));
+    st.add(reinterpret_cast<char**>(&ctl), std::vector<char>(sizeof(bos::dev::LmControl), 0));
+    st.add(reinterpret_cast<char**>(&trace), std::vector<char>(sizeof(bos_lm_iteration) * (size_t)kLmTraceCap, 0));
+    auto undo = [&](int code, const std::string& msg) {
+        if (s->lm_arena) (void)hipFree(s->lm_arena);
+        if (s->lm_hctl) (void)hipHostFree(s->lm_hctl);
+        (void)hipGetLastError();
+        s->lm_arena = nullptr;
+        s->lm_hctl = s->lm_mctl = nullptr;
+        for (auto& f : st.fields) *f.first = nullptr;
+        return fail(code, msg);
+    };
+    const size_t bytes = st.host.size();
+    if (hipMalloc((void**)&s->lm_arena, bytes) != hipSuccess)
+        return undo(BOS_ERR_DEVICE, "bos_optimize / bos_cost: cannot allocate " + std::to_string(bytes) + " bytes");
+    if (hipMemcpy(s->lm_arena, st.host.data(), bytes, hipMemcpyHostToDevice) != hipSuccess)
+        return undo(BOS_ERR_DEVICE, "bos_optimize / bos_cost: upload failed");
+    if (hipHostMalloc((void**)&s->lm_hctl, sizeof(bos::dev::LmControl), hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess ||
+        hipHostGetDevicePointer((void**)&s->lm_mctl, s->lm_hctl, 0) != hipSuccess)
+        return undo(BOS_ERR_DEVICE, "bos_optimize / bos_cost: host-mapped status allocation failed");
+    std::memset(s->lm_hctl, 0, sizeof(bos::dev::LmControl));
+    for (auto& f : st.fields) *f.first = s->lm_arena + f.second;
+    s->lm_ctl = static_cast<bos::dev::LmControl*>(ctl);
+    s->lm_trace = static_cast<bos_lm_iteration*>(trace);
+    return BOS_OK;
+}
+
+// the objective's constant terms: the odometry self-loops (e = -z whatever the state), in fp64
+void lm_loop_terms(const bos_solver* s, double& F, double& chi, int32_t& nrob) {
+    F = chi = 0.0;
+    nrob = 0;
+    for (size_t i = 0; i < s->loop_z.size() / 3; ++i) {
+        const double* z = &s->loop_z[3 * i];
+        const double* u = &s->loop_om[6 * i];
+        const double e0 = 0.0 - z[0], e1 = 0.0 - z[1];
+        const double e2 = bos::normalized_angle<double>(bos::normalized_angle<double>(0.0) - z[2]);
+        const double Oe0 = u[0] * e0 + u[1] * e1 + u[2] * e2;
+        const double Oe1 = u[1] * e0 + u[3] * e1 + u[4] * e2;
+        const double Oe2 = u[2] * e0 + u[4] * e1 + u[5] * e2;
+        const double rho = e0 * Oe0 + e1 * Oe1 + e2 * Oe2;
+        chi += rho;
+        if (rho > s->kt) ++nrob;
+        F += bos::lm_huber(rho, s->kt, rho > s->kt ? std::sqrt(s->kt * rho) : 0.0);
+    }
+}
+
+// the fp64 cost pass at the master state (partials; the decision launch sums them)
+int enqueue_lm_cost(bos_solver* s) {
+    bos::dev::CostParams c;
+    c.NP = s->NP; c.NL = s->NL; c.Mb = s->Mb; c.Mo = s->Mo;
+    c.pose = s->d_pose; c.lm = s->d_lm;
+    c.b_pose = s->tri_pose; c.b_lm = s->lm_blm; c.b_z = s->tri_z; c.b_w = s->lm_bw;
+    c.o_src = s->o_src; c.o_dst = s->o_dst; c.o_z = s->lm_oz; c.o_om = s->lm_oom;
+    c.kt = s->kt;
+    c.part_F = s->lm_pF; c.part_chi = s->lm_pchi; c.part_nrob = s->lm_pnrob;
+    c.n_parts = bos::dev::lm_cost_parts(s->Mb, s->Mo);
+    HIP_TRY(bos::dev::launch_lm_cost(c, s->stream));
+    return BOS_OK;
+}
+
+int enqueue_lm_decide(bos_solver* s, int mode) {
+    bos::dev::DecideParams d;
+    d.part_F = s->lm_pF; d.part_chi = s->lm_pchi; d.part_nrob = s->lm_pnrob;
+    d.n_cost = bos::dev::lm_cost_parts(s->Mb, s->Mo);
+    lm_loop_terms(s, d.F_const, d.chi_const, d.nrob_const);
+    d.part_xx = s->lm_pxx; d.part_xb = s->lm_pxb;
+    d.n_model = bos::dev::lm_model_parts(s->plan.n);
+    d.max_part = s->d_maxpart;
+    d.n_max = (s->NP + s->NL + bos::dev::kUpdateBlock - 1) / bos::dev::kUpdateBlock;
+    d.info = mode == 0 && uses_mf(s) ? bos::dev::mf_info_ptr(s->mf) : nullptr;
+    d.lambda_fp32 = s->precision == BOS_FP32 ? 1 : 0;
+    d.ctl = s->lm_ctl;
+    d.mirror = s->lm_mctl;
+    d.trace = s->lm_trace;
+    d.mode = mode;
+    HIP_TRY(bos::dev::launch_lm_decide(d, s->stream));
+    return BOS_OK;
+}
+
+bos::dev::CopySet lm_copy_set(const bos_solver* s, bool restore) {
+    bos::dev::CopySet c;
+    void* state[5] = {s->d_pose, s->d_lm, s->d_pc, s->d_pth, s->d_lc};
+    lm_state_words(s, c.words);
+    for (int a = 0; a < 5; ++a) {
+        c.dst[a] = restore ? static_cast<uint32_t*>(state[a]) : s->lm_backup[a];
+        c.src[a] = restore ? s->lm_backup[a] : static_cast<const uint32_t*>(state[a]);
+        if (!c.dst[a] || !c.src[a]) c.words[a] = 0;
+    }
+    return c;
+}
+
+// The device work of one LM iteration (multifrontal handles, one GPU): the undamped J+H, lambda from
+// device memory onto its diagonal (the same launch backs the state up), the step's own solve, the
+// model's predicted reduction, the trial box-plus, the fp64 cost of the trial state, the decision (host/lm_rule.hpp) and
+// the rollback of a rejected trial. Every argument is fixed (the kernel threshold is baked in, as in
+// the step's graphs): captured once and replayed.
+int enqueue_lm_iteration(bos_solver* s) {
+    int rc;
+    const bos::Plan& P = s->plan;
+    const bool f32 = s->precision == BOS_FP32;
+    const int64_t nb = 3 * (int64_t)s->NP + 2 * (int64_t)s->NL;
+    const int n_groups = (int)P.blk.lane_pose.size(), n_lanes = (int)P.blk.lm_lane_lm.size();
+    const int32_t* lane_pose = s->lane_identity ? nullptr : s->lane_pose;
+    if ((rc = enqueue_linearize(s, nullptr, true))) return rc;
+    const bos::dev::CopySet backup = lm_copy_set(s, false);
+    HIP_TRY(f32 ? bos::dev::launch_lm_damping<float>((float*)s->d_val, P.blk.size, P.blk.off_ldiag, lane_pose, n_groups, s->NP,
+                                                     s->lm_lane_lm, n_lanes, s->NL, s->lm_ctl, backup, s->stream)
+                : bos::dev::launch_lm_damping<double>((double*)s->d_val, P.blk.size, P.blk.off_ldiag, lane_pose, n_groups,
+                                                      s->NP, s->lm_lane_lm, n_lanes, s->NL, s->lm_ctl, backup, s->stream));
+    bool analysed_now = false;
+    if ((rc = enqueue_solve(s, analysed_now))) return rc;
+    HIP_TRY(f32 ? bos::dev::launch_lm_model<float>(s->d_rhs, (const float*)s->d_b, s->elim_ref, P.n, nb, s->lm_pxx, s->lm_pxb,
+                                                   s->stream)
+                : bos::dev::launch_lm_model<double>(s->d_rhs, (const double*)s->d_b, s->elim_ref, P.n, nb, s->lm_pxx,
+                                                    s->lm_pxb, s->stream));
+    if ((rc = enqueue_update(s)) || (rc = enqueue_lm_cost(s)) || (rc = enqueue_lm_decide(s, 0))) return rc;
+    HIP_TRY(bos::dev::launch_lm_copy(lm_copy_set(s, true), s->lm_ctl, s->stream));
+    return BOS_OK;
+}
+
+int launch_lm_iteration(bos_solver* s) {
+    int rc;
+    if (!s->lm_exec && !s->graph_failed && (rc = capture(s, -3, &s->lm_graph, &s->lm_exec))) return rc;
+    if (s->lm_exec) HIP_TRY(hipGraphLaunch(s->lm_exec, s->stream));
+    else if ((rc = enqueue_lm_iteration(s))) return rc;
+    return BOS_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1124,10 +1328,12 @@ int bos_destroy(bos_solver* s) {
                     s->d_maxpart, s->tri_ptr, s->tri_obs, s->tri_pose, s->tri_z, s->tri_scr,
                     s->scrub, s->lane_pose, s->ex1_send, s->obs ? s->ex1_recv : nullptr, s->ex2_send, s->mailbox,
                     s->d_peers, s->ex1_pack, s->hdr1,
-                    s->ex1_unpack, s->ex2_bnd, s->ex2_usrc, s->ex2_udst, s->upd_nodes, s->abs_part, s->jh_arena};
+                    s->ex1_unpack, s->ex2_bnd, s->ex2_usrc, s->ex2_udst, s->upd_nodes, s->abs_part, s->jh_arena,
+                    s->lm_arena};
     for (void* b : bufs)
         if (b) (void)hipFree(b);
     if (s->h_status) (void)hipHostFree(s->h_status);
+    if (s->lm_hctl) (void)hipHostFree(s->lm_hctl);
     for (void* m : s->peer_maps) (void)hipIpcCloseMemHandle(m);
     if (s->rf) rocsolver_destroy_rfinfo(s->rf);
     if (s->mf) bos::dev::mf_destroy(s->mf);
@@ -1393,6 +1599,15 @@ int bos_create(const bos_problem* pb, const bos_options* opt_in, bos_solver** ou
             om.resize(12);
             s->om_stride = 0;
         }
+        // the cost pass of bos_cost / bos_optimize reads them in fp64 whatever T is (uploaded at its first use)
+        s->h_oz.assign(pb->odom_z, pb->odom_z + 3 * (size_t)s->Mo);
+        s->h_oom.resize(6 * (size_t)s->Mo);
+        for (int k = 0; k < s->Mo; ++k) {
+            const double* m = pb->odom_omega + 9 * (size_t)k;
+            const double u[6] = {m[0], m[1], m[2], m[4], m[5], m[8]};
+            std::memcpy(&s->h_oom[6 * (size_t)k], u, sizeof(u));
+        }
+        if (s->has_w) s->h_bw.assign(pb->bearing_omega, pb->bearing_omega + s->Mb);
         stage.add(&s->o_src, os); stage.add(&s->o_dst, od); stage_Tv(&s->o_z, oz); stage_Tv(&s->o_om, om);
     }
     if ((rc = flush_stage(s, stage))) return bail(rc);
@@ -1995,6 +2210,104 @@ int bos_marginals_timing(const bos_solver* s, double ms[4], int64_t* sigma_bytes
     if (!s || !ms) return fail(BOS_ERR_INVALID, "null argument");
     for (int i = 0; i < 4; ++i) ms[i] = s->marg_ms[i];
     if (sigma_bytes) *sigma_bytes = s->mf ? bos::dev::mf_selinv_sigma_bytes(s->mf) : 0;
+    return BOS_OK;
+}
+
+void bos_lm_default_options(bos_lm_options* o) {
+    if (o) bos::lm_default_options(*o);
+}
+
+int bos_cost(bos_solver* s, double* cost, double* chi2, int32_t* n_robust) {
+    if (!s) return fail(BOS_ERR_INVALID, "null handle");
+    if (lm_sharded(s)) return fail(BOS_ERR_UNSUPPORTED, "bos_cost on a sharded handle (a rank's state is current on its own nodes only)");
+    HIP_TRY(hipSetDevice(s->device));
+    int rc;
+    if ((rc = lm_setup(s)) || (rc = enqueue_lm_cost(s)) || (rc = enqueue_lm_decide(s, 2))) return rc;
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    bos::dev::LmControl h;
+    std::memcpy(&h, (const void*)s->lm_hctl, sizeof(h));
+    if (cost) *cost = h.cost_eval;
+    if (chi2) *chi2 = h.chi2;
+    if (n_robust) *n_robust = h.n_robust;
+    return BOS_OK;
+}
+
+int bos_time_cost(bos_solver* s, int32_t n, double* ms_per_pass) {
+    if (!s || n <= 0 || !ms_per_pass) return fail(BOS_ERR_INVALID, "bad argument");
+    if (lm_sharded(s)) return fail(BOS_ERR_UNSUPPORTED, "bos_time_cost on a sharded handle");
+    HIP_TRY(hipSetDevice(s->device));
+    int rc;
+    if ((rc = lm_setup(s))) return rc;
+    HIP_TRY(hipEventRecord(s->ev[0], s->stream));
+    for (int i = 0; i < n; ++i)
+        if ((rc = enqueue_lm_cost(s))) return rc;
+    HIP_TRY(hipEventRecord(s->ev[1], s->stream));
+    HIP_TRY(hipEventSynchronize(s->ev[1]));
+    *ms_per_pass = elapsed(s->ev[0], s->ev[1]) / n;
+    return BOS_OK;
+}
+
+int bos_optimize(bos_solver* s, const bos_lm_options* options, bos_lm_result* result, bos_lm_iteration* trace,
+                 int32_t trace_capacity) {
+    if (!s) return fail(BOS_ERR_INVALID, "null handle");
+    if (!uses_mf(s))
+        return fail(BOS_ERR_UNSUPPORTED, "bos_optimize needs a multifrontal solver (BOS_SOLVER_SCHUR or BOS_SOLVER_SUPERNODAL)");
+    if (lm_sharded(s)) return fail(BOS_ERR_UNSUPPORTED, "bos_optimize on a sharded handle");
+    bos_lm_options o;
+    bos::lm_default_options(o);
+    if (options) o = *options;
+    if (o.max_iterations < 1 || o.max_iterations > kLmTraceCap) return fail(BOS_ERR_INVALID, "bos_optimize: max_iterations must be 1 .. 4096");
+    if (o.check_every < 1) return fail(BOS_ERR_INVALID, "bos_optimize: check_every must be >= 1");
+    if (!(o.lambda0 >= 0.0) || !(o.lambda_min > 0.0) || !(o.lambda_max >= o.lambda_min) || !(o.dx_tol >= 0.0) || !(o.f_tol >= 0.0))
+        return fail(BOS_ERR_INVALID, "bos_optimize: bad lambda0 / lambda_min / lambda_max / dx_tol / f_tol");
+    if (trace_capacity < 0 || (trace_capacity > 0 && !trace)) return fail(BOS_ERR_INVALID, "bos_optimize: trace_capacity without a trace");
+    HIP_TRY(hipSetDevice(s->device));
+    int rc;
+    if ((rc = lm_setup(s))) return rc;
+    // bos_step returns on its status word, before the stream has drained
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    bos::dev::LmControl h;
+    std::memset(&h, 0, sizeof(h));
+    h.opt = o;
+    if (o.lambda0 > 0.0) {
+        h.st.lambda = o.lambda0;
+        h.st.nu = 2.0;
+    } else {
+        h.st.lambda = s->lm_started ? s->lm_lambda : s->damping;
+        h.st.nu = s->lm_started ? s->lm_nu : 2.0;
+    }
+    h.trace_cap = kLmTraceCap;
+    h.seq = s->lm_hctl->seq;
+    HIP_TRY(hipMemcpy(s->lm_ctl, &h, sizeof(h), hipMemcpyHostToDevice));
+    s->have_dx = false;   // d_rhs will hold the last trial's solution, accepted or not
+    if ((rc = enqueue_lm_cost(s)) || (rc = enqueue_lm_decide(s, 1))) return rc;
+    int enqueued = 0;
+    while (enqueued < o.max_iterations) {
+        const int batch = std::min<int>(o.check_every, o.max_iterations - enqueued);
+        for (int i = 0; i < batch; ++i)
+            if ((rc = launch_lm_iteration(s))) return rc;
+        enqueued += batch;
+        HIP_TRY(hipStreamSynchronize(s->stream));
+        std::memcpy(&h, (const void*)s->lm_hctl, sizeof(h));
+        if (h.st.done) break;
+    }
+    s->lm_started = true;
+    s->lm_lambda = h.st.lambda;
+    s->lm_nu = h.st.nu;
+    if (result) {
+        result->iterations = h.st.iteration;
+        result->accepted = h.st.accepted;
+        result->rejected = h.st.rejected;
+        result->reason = h.st.reason;
+        result->cost_initial = h.cost_start;
+        result->cost_final = h.st.cost;
+        result->lambda_final = h.st.lambda;
+    }
+    const int32_t nrec = std::min<int32_t>(h.st.iteration, trace_capacity);
+    if (trace && nrec > 0) HIP_TRY(hipMemcpy(trace, s->lm_trace, (size_t)nrec * sizeof(bos_lm_iteration), hipMemcpyDeviceToHost));
+    if (h.aborted)
+        return fail(BOS_ERR_SOLVER, "sparse factorization aborted: a dataflow dependency wait timed out (state at the "
+                                    "last accepted iterate)");
     return BOS_OK;
 }
 

@@ -16,6 +16,7 @@
 #include "bos_math.hpp"
 #include "error.hpp"
 #include "host_mf.hpp"
+#include "lm_rule.hpp"
 #include "plan.hpp"
 
 struct bos_cpu_gn {
@@ -27,6 +28,9 @@ struct bos_cpu_gn {
     std::vector<int32_t> b_pose, b_lm, o_src, o_dst;
     std::vector<double> b_z, b_w, o_z, o_om;   // o_om: upper triangle (00, 01, 02, 11, 12, 22)
     double kt = 1.0, damping = 0.01;
+    // bos_cpu_gn_optimize: the last call's final lambda / nu (lambda0 = 0 continues from them)
+    bool lm_started = false;
+    double lm_lambda = 0.0, lm_nu = 2.0;
 };
 
 namespace {
@@ -191,8 +195,12 @@ int bos_cpu_gn_create(const bos_problem* pb, int32_t solver, int32_t threads, bo
     return BOS_OK;
 }
 
-int bos_cpu_gn_step(bos_cpu_gn* c, double* chi2) {
-    if (!c) return cfail(BOS_ERR_INVALID, "null handle");
+}  // extern "C"
+
+namespace {
+
+// J+H into the block array and b; returns chi^2
+double cpu_build(bos_cpu_gn* c) {
     const bos::Plan& P = c->plan;
     bos::Pool& pool = *c->pool;
     const int G = (int)P.blk.lane_pose.size(), NLL = (int)P.blk.lm_lane_lm.size();
@@ -211,24 +219,44 @@ int bos_cpu_gn_step(bos_cpu_gn* c, double* chi2) {
                                   u[2] * e[0] + u[4] * e[1] + u[5] * e[2]};
             chi += e[0] * Oe[0] + e[1] * Oe[1] + e[2] * Oe[2];
         }
-    if (chi2) *chi2 = chi;
-    // solve H_nf x = b_nf (rhs in elimination order), dx = -x
-    bos::HostMf& M = *c->mf;
-    const int64_t n = P.n;
-    std::vector<int32_t> ref(n);
+    return chi;
+}
+
+// permuted dof -> reference dof
+std::vector<int32_t> cpu_ref_dof(const bos_cpu_gn* c) {
+    const bos::Plan& P = c->plan;
+    std::vector<int32_t> ref(P.n);
     for (int u = 0; u < c->NP + c->NL; ++u) {
         if (u == P.fixed) continue;
         const int sz = u < c->NP ? 3 : 2;
         const int r0 = u < c->NP ? 3 * u : 3 * c->NP + 2 * (u - c->NP);
         for (int d = 0; d < sz; ++d) ref[P.node_dof[u] + d] = r0 + d;
     }
-    for (int64_t i = 0; i < n; ++i) M.x[i] = c->b[ref[i]];
+    return ref;
+}
+
+// solve H_nf x = b_nf (rhs in elimination order), dx = -x; returns the count of non-positive pivots
+int cpu_solve(bos_cpu_gn* c, const std::vector<int32_t>& ref) {
+    bos::HostMf& M = *c->mf;
+    for (int64_t i = 0; i < c->plan.n; ++i) M.x[i] = c->b[ref[i]];
     auto all = [](int) { return true; };
+    M.nonpos = 0;
     M.factor(all);
     M.forward(all);
     M.backward(all);
-    // box-plus (framework/state.cpp:69-80)
-    pool.parallel_for(c->NP + c->NL, [&](int64_t u) {
+    return M.nonpos;
+}
+
+// box-plus (framework/state.cpp:69-80); returns max |dx| (NaN if the update is not finite)
+double cpu_update(bos_cpu_gn* c) {
+    const bos::Plan& P = c->plan;
+    bos::HostMf& M = *c->mf;
+    double m = 0.0;
+    for (int64_t i = 0; i < P.n; ++i) {
+        const double a = std::fabs(M.x[i]);
+        m = (a != a || m != m) ? a + m : std::max(m, a);
+    }
+    c->pool->parallel_for(c->NP + c->NL, [&](int64_t u) {
         if (u == P.fixed) return;
         const int d = P.node_dof[u];
         if (u < c->NP) {
@@ -240,7 +268,142 @@ int bos_cpu_gn_step(bos_cpu_gn* c, double* chi2) {
             l[1] += -M.x[d + 1];
         }
     });
+    return m;
+}
+
+// F, chi^2 and the robust count at the current state: every bearing and odometry edge once, self-loops
+// included (bos.h bos_cost)
+void cpu_cost(const bos_cpu_gn* c, double& F, double& chi, int32_t& nrob) {
+    F = chi = 0.0;
+    nrob = 0;
+    auto add = [&](double rho) {
+        chi += rho;
+        if (rho > c->kt) ++nrob;
+        F += bos::lm_huber(rho, c->kt, rho > c->kt ? std::sqrt(c->kt * rho) : 0.0);
+    };
+    for (size_t k = 0; k < c->b_z.size(); ++k) {
+        const double* p = &c->pose[3 * (size_t)c->b_pose[k]];
+        const double* l = &c->lm[2 * (size_t)c->b_lm[k]];
+        double gx, gy;
+        const double e = bos::bearing_error<double>(p[0], p[1], std::cos(p[2]), std::sin(p[2]), l[0], l[1], c->b_z[k], gx, gy);
+        const double w = c->b_w.empty() ? 1.0 : c->b_w[k];
+        add(e * w * e);
+    }
+    for (size_t k = 0; k < c->o_src.size(); ++k) {
+        const double* s = &c->pose[3 * (size_t)c->o_src[k]];
+        const double* d = &c->pose[3 * (size_t)c->o_dst[k]];
+        const double* z = &c->o_z[3 * k];
+        const double* u = &c->o_om[6 * k];
+        double e[3], J[18];
+        if (c->o_src[k] == c->o_dst[k]) {
+            e[0] = -z[0]; e[1] = -z[1]; e[2] = bos::normalized_angle<double>(-z[2]);
+        } else {
+            bos::odometry_error_jacobian<double>(s[0], s[1], s[2], std::cos(s[2]), std::sin(s[2]), d[0], d[1], d[2], z[0], z[1],
+                                                 z[2], e, J);
+        }
+        const double Oe[3] = {u[0] * e[0] + u[1] * e[1] + u[2] * e[2], u[1] * e[0] + u[3] * e[1] + u[4] * e[2],
+                              u[2] * e[0] + u[4] * e[1] + u[5] * e[2]};
+        add(e[0] * Oe[0] + e[1] * Oe[1] + e[2] * Oe[2]);
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+int bos_cpu_gn_step(bos_cpu_gn* c, double* chi2) {
+    if (!c) return cfail(BOS_ERR_INVALID, "null handle");
+    const double chi = cpu_build(c);
+    if (chi2) *chi2 = chi;
+    cpu_solve(c, cpu_ref_dof(c));
+    cpu_update(c);
     return BOS_OK;
+}
+
+int bos_cpu_gn_set_kernel_threshold(bos_cpu_gn* c, double kt) {
+    if (!c) return cfail(BOS_ERR_INVALID, "null handle");
+    c->kt = kt;
+    return BOS_OK;
+}
+
+int bos_cpu_gn_cost(bos_cpu_gn* c, double* cost, double* chi2, int32_t* n_robust) {
+    if (!c) return cfail(BOS_ERR_INVALID, "null handle");
+    double F, chi;
+    int32_t nrob;
+    cpu_cost(c, F, chi, nrob);
+    if (cost) *cost = F;
+    if (chi2) *chi2 = chi;
+    if (n_robust) *n_robust = nrob;
+    return BOS_OK;
+}
+
+int bos_cpu_gn_optimize(bos_cpu_gn* c, const bos_lm_options* options, bos_lm_result* result, bos_lm_iteration* trace,
+                        int32_t trace_capacity) {
+    if (!c) return cfail(BOS_ERR_INVALID, "null handle");
+    bos_lm_options o;
+    bos::lm_default_options(o);
+    if (options) o = *options;
+    if (o.max_iterations < 1 || o.max_iterations > 4096) return cfail(BOS_ERR_INVALID, "max_iterations must be 1 .. 4096");
+    if (!(o.lambda0 >= 0.0) || !(o.lambda_min > 0.0) || !(o.lambda_max >= o.lambda_min) || !(o.dx_tol >= 0.0) || !(o.f_tol >= 0.0))
+        return cfail(BOS_ERR_INVALID, "bad lambda0 / lambda_min / lambda_max / dx_tol / f_tol");
+    if (trace_capacity < 0 || (trace_capacity > 0 && !trace)) return cfail(BOS_ERR_INVALID, "trace_capacity without a trace");
+    const bos::Plan& P = c->plan;
+    const bos::BlockLayout& B = P.blk;
+    bos_lm_state st;
+    std::memset(&st, 0, sizeof(st));
+    st.lambda = o.lambda0 > 0.0 ? o.lambda0 : (c->lm_started ? c->lm_lambda : c->damping);
+    st.nu = o.lambda0 > 0.0 || !c->lm_started ? 2.0 : c->lm_nu;
+    double chi;
+    int32_t nrob;
+    cpu_cost(c, st.cost, chi, nrob);
+    const double cost_initial = st.cost;
+    const std::vector<int32_t> ref = cpu_ref_dof(c);
+    const double damping = c->damping;
+    while (!st.done) {
+        // H0 and b without damping, then lambda on the diagonal of the blocks the J+H wrote
+        c->damping = 0.0;
+        cpu_build(c);
+        c->damping = damping;
+        double* hv = c->mf->hval.data();
+        for (int32_t p : B.lane_pose)
+            if (p >= 0) { hv[6 * (int64_t)p] += st.lambda; hv[6 * (int64_t)p + 2] += st.lambda; hv[6 * (int64_t)p + 5] += st.lambda; }
+        for (int32_t l : B.lm_lane_lm) { hv[B.off_ldiag + 3 * (int64_t)l] += st.lambda; hv[B.off_ldiag + 3 * (int64_t)l + 2] += st.lambda; }
+        const int info = cpu_solve(c, ref);
+        double xx = 0.0, xb = 0.0;
+        for (int64_t i = 0; i < P.n; ++i) {
+            xx += c->mf->x[i] * c->mf->x[i];
+            xb += c->mf->x[i] * c->b[ref[i]];
+        }
+        const double pred = st.lambda * xx + xb;
+        const std::vector<double> pose0 = c->pose, lm0 = c->lm;
+        const double max_dx = cpu_update(c);
+        double F;
+        cpu_cost(c, F, chi, nrob);
+        bos_lm_iteration rec;
+        const int32_t slot = st.iteration;
+        bos::lm_rule_apply(st, o, F, pred, max_dx, info, &rec);
+        if (!rec.accepted) { c->pose = pose0; c->lm = lm0; }
+        if (trace && slot < trace_capacity) trace[slot] = rec;
+    }
+    c->lm_started = true;
+    c->lm_lambda = st.lambda;
+    c->lm_nu = st.nu;
+    if (result) {
+        result->iterations = st.iteration;
+        result->accepted = st.accepted;
+        result->rejected = st.rejected;
+        result->reason = st.reason;
+        result->cost_initial = cost_initial;
+        result->cost_final = st.cost;
+        result->lambda_final = st.lambda;
+    }
+    return BOS_OK;
+}
+
+int bos_lm_rule_apply(bos_lm_state* state, const bos_lm_options* options, double cost_trial, double predicted,
+                      double max_abs_dx, int32_t solver_info, bos_lm_iteration* record) {
+    if (!state || !options) return cfail(BOS_ERR_INVALID, "null argument");
+    return bos::lm_rule_apply(*state, *options, cost_trial, predicted, max_abs_dx, solver_info, record) ? 1 : 0;
 }
 
 int bos_cpu_gn_get_state(const bos_cpu_gn* c, double* pose_xyt, double* landmark_xy) {

@@ -95,6 +95,9 @@ struct HostMf {
     std::vector<double> hval, L, U, u, x;
     std::vector<std::vector<double>> fwv;
     Pool* pool = nullptr;
+    // non-positive pivots met by factor() since the caller last cleared it (the GPU solver's info word)
+    int nonpos = 0;   // (added to atomically: a level's fronts run in parallel)
+    void count_nonpos(int k) { if (k) __atomic_fetch_add(&nonpos, k, __ATOMIC_RELAXED); }
 
     HostMf(const Plan& plan, Pool* p = nullptr)
         : P(plan), F(plan.mf), hval(plan.blk.size, 0.0), L(plan.mf.L_size), U(plan.mf.U_size), u(plan.mf.u_size),
@@ -134,6 +137,7 @@ struct HostMf {
                 const int col0 = rec[5], t = rec[6] & 63, rc = (rec[6] >> 6) & 63;
                 const double l00 = std::sqrt(std::max(v(rec[2]), 1e-300)), l10 = v(rec[3]) / l00;
                 const double l11 = std::sqrt(std::max(v(rec[4]) - l10 * l10, 1e-300));
+                if (t == 0) count_nonpos((v(rec[2]) > 0.0 ? 0 : 1) + (v(rec[4]) - l10 * l10 > 0.0 ? 0 : 1));
                 const double y0 = x[col0] / l00, y1 = (x[col0 + 1] - l10 * y0) / l11;
                 double* Lc = L.data() + rec[7];
                 const int mc = 2 + rc;
@@ -185,6 +189,7 @@ struct HostMf {
                 for (int i = j; i < rc2; ++i) W[map[i] + (size_t)map[j] * m] += U[F.U_off[c] + mf_packed(i, j, rc2)];
         }
         for (int j = 0; j < k; ++j) {
+            if (!(W[j + (size_t)j * m] > 0.0)) count_nonpos(1);
             const double d = std::sqrt(std::max(W[j + (size_t)j * m], 1e-300));
             W[j + (size_t)j * m] = d;
             for (int i = j + 1; i < m; ++i) W[i + (size_t)j * m] /= d;
