@@ -200,6 +200,41 @@ int bos_debug_set_step_graph(struct bos_solver* s, int32_t enable);
  * 100 MHz. meta[4 * nsuper] = tree level (-1 folded), k, r, folded children. */
 int bos_debug_solver_stamps(struct bos_solver* s, int64_t capacity, uint64_t* stamps, int32_t* meta);
 
+/* Diagnostics: the kernel route every front of the multifrontal tree takes in this handle's launch
+ * sequence. One value per launch site of the factorization (mf_factor_t) and of the backward
+ * substitution (mf_solve) in hip/multifrontal.hip; the launch sites themselves note it, with the
+ * front list they launch, the first time the sequence is enqueued (a replayed graph enqueues it
+ * once, at capture). Nothing is launched or changed by the call. */
+enum {
+    BOS_ROUTE_NONE = -1,          /* no launch of this handle processes the front (another rank's)   */
+    BOS_ROUTE_F_REG16 = 0,        /* mf_factor_reg<16>, main stream                                   */
+    BOS_ROUTE_F_REG16_SIDE = 1,   /* mf_factor_reg<16> behind the class-64 launch on the side stream */
+    BOS_ROUTE_F_PAN48 = 2,        /* class-48 launch (17-48 rows): mf_factor_pan<48>                  */
+    BOS_ROUTE_F_PAN64 = 3,        /* class-64 launch (49-64 rows): mf_factor_pan<64>, main stream     */
+    BOS_ROUTE_F_PAN64_SIDE = 4,   /* the same on the side stream                                     */
+    BOS_ROUTE_F_BLK = 5,          /* mf_factor_blk (65-128 rows), main stream                         */
+    BOS_ROUTE_F_BLK_SIDE2 = 6,    /* mf_factor_blk on the second side stream                          */
+    BOS_ROUTE_F_MIXB_BLK = 7,     /* mf_factor_mixb, a blocked front                                  */
+    BOS_ROUTE_F_MIXB_WAVE = 8,    /* mf_factor_mixb, a wave front                                     */
+    BOS_ROUTE_F_LEVEL = 9,        /* mf_factor_level + mf_forward_level (above 128 rows)              */
+    BOS_ROUTE_F_FLOW = 10,        /* mf_factor_flow (dataflow launch over the top of the tree)        */
+    BOS_ROUTE_F_FOLDED = 11,      /* a landmark folded into its parent front by the parent's kernel   */
+    BOS_ROUTE_F_COUNT = 12
+};
+enum {
+    BOS_ROUTE_B_FLOW = 0,         /* mf_backward_flow  */
+    BOS_ROUTE_B_WAVE = 1,         /* mf_backward_wave  */
+    BOS_ROUTE_B_LEVEL = 2,        /* mf_backward_level */
+    BOS_ROUTE_B_FOLD = 3,         /* mf_backward_fold  */
+    BOS_ROUTE_B_COUNT = 4
+};
+/* routes[4 * nsuper] = per front: factor route, backward route, k (columns), r (update rows); fronts
+ * in the plan's supernode order; *nsuper (may be NULL) = their number. routes NULL with capacity 0:
+ * only *nsuper is returned. BOS_ERR_UNSUPPORTED for a handle without the multifrontal solver,
+ * BOS_ERR_INVALID before the handle's first bos_step (the sequence has not been enqueued yet) or
+ * when capacity < 4 * nsuper. */
+int bos_debug_solver_routes(struct bos_solver* s, int64_t capacity, int32_t* routes, int32_t* nsuper);
+
 /* Diagnostics: one J+H launch with per-wave timeline stamps, 8 x uint64 per wave: block, wave in
  * block, kind (0 pose lanes / 1 landmark lanes), t_start, t_loop, t_loop_end, t_end (realtime clock,
  * 100 MHz ticks), hw_id | xcc_id << 32. capacity in waves; *n_waves = waves of the launch;

@@ -51,6 +51,7 @@ EXPORTED_SYMBOLS = [
     "bos_plan_node_owner", "bos_step_phase", "bos_exchange_size", "bos_exchange_download", "bos_exchange_upload",
     "bos_node_owner",
     "bos_debug_set_g2o_parser", "bos_debug_inject_stall", "bos_debug_set_step_graph", "bos_debug_solver_stamps",
+    "bos_debug_solver_routes",
     "bos_time_linearize", "bos_time_triangulate", "bos_time_steps", "bos_cpu_gn_create", "bos_cpu_gn_step", "bos_cpu_gn_get_state",
     "bos_cpu_gn_destroy", "bos_normalized_angle_f64", "bos_normalized_angle_f32", "bos_exchange_p2p_handle",
     "bos_exchange_p2p_connect", "bos_time_facade_steps", "bos_debug_facade_selftest", "bos_set_exchange_timeout",
@@ -230,6 +231,7 @@ def lib():
         "bos_debug_set_g2o_parser": (None, [ctypes.c_int32]),
         "bos_debug_inject_stall": (ctypes.c_int, [vp]),
         "bos_debug_set_step_graph": (ctypes.c_int, [vp, ctypes.c_int32]),
+        "bos_debug_solver_routes": (ctypes.c_int, [vp, ctypes.c_int64, _ip, _ip]),
         "bos_debug_solver_stamps": (ctypes.c_int, [vp, ctypes.c_int64, ctypes.POINTER(ctypes.c_uint64),
                                                    ctypes.POINTER(ctypes.c_int32)]),
         "bos_time_linearize": (ctypes.c_int, [vp, ctypes.c_int32, ctypes.c_int32, _dp]),
@@ -757,6 +759,22 @@ class Solver:
         _check(lib().bos_debug_solver_stamps(self._h, st.size, st.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)),
                                              meta.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))), "solver stamps")
         return st, meta
+
+    # bos_host.h BOS_ROUTE_F_* / BOS_ROUTE_B_*, by value
+    FACTOR_ROUTES = ("reg16", "reg16_side", "pan48", "pan64", "pan64_side", "blk", "blk_side2", "mixb_blk",
+                     "mixb_wave", "level", "flow", "folded")
+    BACKWARD_ROUTES = ("backward_flow", "backward_wave", "backward_level", "backward_fold")
+
+    def debug_solver_routes(self) -> np.ndarray:
+        """Diagnostics: [nsuper, 4] = factor route (FACTOR_ROUTES index), backward route
+        (BACKWARD_ROUTES index), k, r of every front, as the launch sites noted them when the handle's
+        first step was enqueued (bos_host.h bos_debug_solver_routes; BosError before that step)."""
+        n = ctypes.c_int32(0)
+        _check(lib().bos_debug_solver_routes(self._h, 0, None, ctypes.byref(n)), "bos_debug_solver_routes")
+        out = np.zeros((n.value, 4), dtype=np.int32)
+        _check(lib().bos_debug_solver_routes(self._h, out.size, _ptr(out, ctypes.c_int32), ctypes.byref(n)),
+               "bos_debug_solver_routes")
+        return out
 
     def debug_set_step_graph(self, enable: bool):
         """Test hook: GN steps as individual launches (False) or the captured graph (True, default)."""

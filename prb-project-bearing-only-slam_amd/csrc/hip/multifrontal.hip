@@ -26,6 +26,7 @@
 #include <type_traits>
 #include <vector>
 
+#include "../../../include/bos_host.h"
 #include "../host/plan.hpp"
 #include "multifrontal.hpp"
 #include "selinv.hpp"
@@ -2292,6 +2293,10 @@ struct Prog {
     std::vector<int32_t> bptr;
     std::vector<int> blds;
     int32_t* blist = nullptr;
+    // host copies of list / order_factor / order_bwd / fold_list / blist: what the launch sites note
+    // into the route report (MfDevice::note)
+    std::vector<int32_t> h_list, h_order_factor, h_order_bwd, h_fold_list, h_blist;
+    const int32_t* hl(int lev, int c) const { return h_list.data() + ptr[lev * kClasses + c]; }
     int count(int lev, int c0, int c1) const { return ptr[lev * kClasses + c1] - ptr[lev * kClasses + c0]; }
     int count(int lev, int c) const { return count(lev, c, c + 1); }
     int lds_max(const std::vector<int>& v, int lev, int c0, int c1) const {
@@ -2361,6 +2366,26 @@ struct MfDevice {
     int64_t* ug_off = nullptr;
     int8_t* xtag = nullptr;
     SelInv* selinv = nullptr;     // selected inverse (hip/selinv.hip): built when marginals are first asked for
+    // Route report (bos_debug_solver_routes): every launch site of mf_factor_t / mf_solve notes its
+    // route (bos_host.h BOS_ROUTE_*) for the fronts of the list it launches, the first time a program's
+    // sequence is enqueued; a front's folded children (the fold_cnt the kernels read) go with it.
+    std::vector<int8_t> route_f, route_b;
+    std::vector<int32_t> h_child_ptr, h_child, h_fold_cnt;
+    bool noted_f[2] = {false, false}, noted_b[2] = {false, false};
+    void note_f(int which, int route, const int32_t* fronts, int n) {
+        if (noted_f[which]) return;
+        for (int i = 0; i < n; ++i) {
+            const int s = fronts[i];
+            route_f[s] = (int8_t)route;
+            if (!h_fold_cnt.empty())
+                for (int ci = h_child_ptr[s]; ci < h_child_ptr[s] + h_fold_cnt[s]; ++ci)
+                    route_f[h_child[ci]] = (int8_t)BOS_ROUTE_F_FOLDED;
+        }
+    }
+    void note_b(int which, int route, const int32_t* fronts, int n) {
+        if (noted_b[which]) return;
+        for (int i = 0; i < n; ++i) route_b[fronts[i]] = (int8_t)route;
+    }
 
     MfArgs args(const Prog& P, int lev, int c, const double* A, double* x) const {
         MfArgs g;
@@ -2487,6 +2512,7 @@ int build_prog(const Multifrontal& F, const std::vector<int8_t>& sel, int id, Pr
     if ((rc = up(&P.list, lst, err)) || (rc = up(&P.order_factor, ofac, err)) || (rc = up(&P.order_bwd, obwd, err)) ||
         (rc = up(&P.fold_list, folds, err)) || (rc = up(&P.blist, blst, err)))
         return rc;
+    P.h_list = lst; P.h_order_factor = ofac; P.h_order_bwd = obwd; P.h_fold_list = folds; P.h_blist = blst;
     return 0;
 }
 
@@ -2503,6 +2529,9 @@ int mf_create(const Multifrontal& F, const int8_t* owner, int rank, MfDevice** o
     *out = d;
     d->nlevels = F.nlevels;
     d->nsuper = F.nsuper;
+    d->route_f.assign(F.nsuper, (int8_t)BOS_ROUTE_NONE);
+    d->route_b.assign(F.nsuper, (int8_t)BOS_ROUTE_NONE);
+    d->h_child_ptr = F.child_ptr; d->h_child = F.child; d->h_fold_cnt = F.fold_cnt;
     std::vector<int64_t> scr(F.nsuper, -1);
     int64_t scratch_size = 0;
     for (int s = 0; s < F.nsuper; ++s) {
@@ -2682,7 +2711,10 @@ hipError_t mf_factor_t(MfDevice* d, int which, const double* A, double* x, hipSt
             const int4 ow = make_int4(0, P.count(l, 0), P.count(l, 0, 2), P.count(l, 0, 3));
             hipLaunchKernelGGL((mf_factor_mixb<F32>), dim3(n4 + nwf), dim3(kMfBlock), std::max(P.lds_blk[l], kMixbWaveLds),
                                s, d->args(P, l, 0, A, x), d->args(P, l, 4, A, x).level, n4, nw, ow);
+            d->note_f(which, BOS_ROUTE_F_MIXB_BLK, P.hl(l, 4), n4);
+            d->note_f(which, BOS_ROUTE_F_MIXB_WAVE, P.hl(l, 0), P.count(l, 0, 4));
             if ((n = P.count(l, 5))) {   // fronts above kBlkMaxM rows (fallback plans)
+                d->note_f(which, BOS_ROUTE_F_LEVEL, P.hl(l, 5), n);
                 hipLaunchKernelGGL(mf_factor_level, dim3(n), dim3(kMfBlock), P.lds_factor[l * kClasses + 5], s,
                                    d->args(P, l, 5, A, x));
                 hipLaunchKernelGGL(mf_forward_level, dim3(n), dim3(kMfBlock), P.lds_fwd[l * kClasses + 5], s,
@@ -2704,6 +2736,7 @@ hipError_t mf_factor_t(MfDevice* d, int which, const double* A, double* x, hipSt
             if ((e = hipStreamWaitEvent(d->side2, d->ev_fork, 0)) != hipSuccess) return e;
             hipLaunchKernelGGL((mf_factor_blk<F32>), dim3(P.count(l, 4)), dim3(kMfBlock), P.lds_blk[l], d->side2,
                                d->args(P, l, 4, A, x));
+            d->note_f(which, BOS_ROUTE_F_BLK_SIDE2, P.hl(l, 4), P.count(l, 4));
             if ((e = hipEventRecord(d->ev_join2, d->side2)) != hipSuccess) return e;
         }
         if (fork) {
@@ -2713,20 +2746,27 @@ hipError_t mf_factor_t(MfDevice* d, int which, const double* A, double* x, hipSt
                                    d->args(P, l, 3, A, x));
             else
                 hipLaunchKernelGGL((mf_factor_reg<64, F32>), dim3(P.count(l, 3)), dim3(64), 0, d->side, d->args(P, l, 3, A, x));
-            if (tiny16 && (n = P.count(l, 0)))
+            d->note_f(which, BOS_ROUTE_F_PAN64_SIDE, P.hl(l, 3), P.count(l, 3));
+            if (tiny16 && (n = P.count(l, 0))) {
                 hipLaunchKernelGGL((mf_factor_reg<16, F32>), dim3(n), dim3(64), 0, d->side, d->args(P, l, 0, A, x));
+                d->note_f(which, BOS_ROUTE_F_REG16_SIDE, P.hl(l, 0), n);
+            }
             if ((e = hipEventRecord(d->ev_join, d->side)) != hipSuccess) return e;
         }
-        if ((n = P.count(l, 0)) && !tiny16)
+        if ((n = P.count(l, 0)) && !tiny16) {
             hipLaunchKernelGGL((mf_factor_reg<16, F32>), dim3(n), dim3(64), 0, s, d->args(P, l, 0, A, x));
-        if ((n = P.count(l, 1))) hipLaunchKernelGGL((mf_factor_reg<32, F32>), dim3(n), dim3(64), 0, s, d->args(P, l, 1, A, x));
+            d->note_f(which, BOS_ROUTE_F_REG16, P.hl(l, 0), n);
+        }
+        // (class 1 has no list of its own: launch_class() sends its fronts to the class-48 launch)
         if ((n = P.count(l, 2))) {
+            d->note_f(which, BOS_ROUTE_F_PAN48, P.hl(l, 2), n);
             if (kPanel48)
                 hipLaunchKernelGGL((mf_factor_pan<48, kPanelKP, F32>), dim3(n), dim3(64), 0, s, d->args(P, l, 2, A, x));
             else
                 hipLaunchKernelGGL((mf_factor_reg<48, F32>), dim3(n), dim3(64), 0, s, d->args(P, l, 2, A, x));
         }
         if ((n = P.count(l, 3)) && !fork) {
+            d->note_f(which, BOS_ROUTE_F_PAN64, P.hl(l, 3), n);
             if (kPanel64)
                 hipLaunchKernelGGL((mf_factor_pan<64, kPanelKP, F32>), dim3(n), dim3(64), 0, s, d->args(P, l, 3, A, x));
             else
@@ -2740,7 +2780,9 @@ hipError_t mf_factor_t(MfDevice* d, int which, const double* A, double* x, hipSt
             if (!(n = P.count(l, c))) continue;
             if (c == 4 && d->blk) {
                 hipLaunchKernelGGL((mf_factor_blk<F32>), dim3(n), dim3(kMfBlock), P.lds_blk[l], s, d->args(P, l, 4, A, x));
+                d->note_f(which, BOS_ROUTE_F_BLK, P.hl(l, 4), n);
             } else {
+                d->note_f(which, BOS_ROUTE_F_LEVEL, P.hl(l, c), n);
                 hipLaunchKernelGGL(mf_factor_level, dim3(n), dim3(kMfBlock), P.lds_factor[l * kClasses + c], s,
                                    d->args(P, l, c, A, x));
                 hipLaunchKernelGGL(mf_forward_level, dim3(n), dim3(kMfBlock), P.lds_fwd[l * kClasses + c], s,
@@ -2754,8 +2796,10 @@ hipError_t mf_factor_t(MfDevice* d, int which, const double* A, double* x, hipSt
                      d->fid_f, P.id, d->stamps};
         const int grid = std::min(P.n_flow_factor, d->ncu * kFlowWavesFactor);
         hipLaunchKernelGGL((mf_factor_flow<F32>), dim3(grid), dim3(64), 0, s, d->args(P, 0, 0, A, x), f);
+        d->note_f(which, BOS_ROUTE_F_FLOW, P.h_order_factor.data(), P.n_flow_factor);
         if ((e = hipGetLastError()) != hipSuccess) return e;
     }
+    d->noted_f[which] = true;
     return hipSuccess;
 }
 
@@ -2780,6 +2824,7 @@ hipError_t mf_solve(MfDevice* d, int which, double* x, hipStream_t s) {
         const int grid = std::min(P.n_flow_solve, d->ncu * kFlowWavesBackward);
         hipLaunchKernelGGL(mf_backward_flow, dim3(grid), dim3(64), P.lds_bwd_flow, s, d->args(P, 0, 0, nullptr, x), fb,
                            (const int32_t*)d->parent);
+        d->note_b(which, BOS_ROUTE_B_FLOW, P.h_order_bwd.data(), P.n_flow_solve);
         if ((e = hipGetLastError()) != hipSuccess) return e;
     }
     for (int l = std::min(P.solve_lev0, d->nlevels) - 1; l >= 0; --l) {
@@ -2789,11 +2834,13 @@ hipError_t mf_solve(MfDevice* d, int which, double* x, hipStream_t s) {
             g.level = P.blist + P.bptr[l];
             g.count = P.bptr[l + 1] - P.bptr[l];
             hipLaunchKernelGGL(mf_backward_wave, dim3(g.count), dim3(64), P.blds[l], s, g);
+            d->note_b(which, BOS_ROUTE_B_WAVE, P.h_blist.data() + P.bptr[l], g.count);
         }
         if ((n = P.count(l, 4, kClasses))) {   // the workgroup fronts (classes 4 and 5, one list)
             MfArgs g = d->args(P, l, 4, nullptr, x);
             g.count = n;
             hipLaunchKernelGGL(mf_backward_level, dim3(n), dim3(kMfBlock), P.lds_max(P.lds_bwd, l, 4, kClasses), s, g);
+            d->note_b(which, BOS_ROUTE_B_LEVEL, P.hl(l, 4), n);
         }
         if ((e = hipGetLastError()) != hipSuccess) return e;
     }
@@ -2802,9 +2849,19 @@ hipError_t mf_solve(MfDevice* d, int which, double* x, hipStream_t s) {
         g.level = P.fold_list;
         g.count = P.n_fold;
         hipLaunchKernelGGL(mf_backward_fold, dim3(((int64_t)P.n_fold * kFoldLanes + kMfBlock - 1) / kMfBlock), dim3(kMfBlock), 0, s, g);
+        d->note_b(which, BOS_ROUTE_B_FOLD, P.h_fold_list.data(), P.n_fold);
         if ((e = hipGetLastError()) != hipSuccess) return e;
     }
+    d->noted_b[which] = true;
     return hipSuccess;
+}
+
+int mf_debug_routes(const MfDevice* d, int8_t* factor, int8_t* backward) {
+    for (int w = 0; w < 2; ++w)
+        if (!d->prog[w].ptr.empty() && (!d->noted_f[w] || !d->noted_b[w])) return -1;
+    std::copy(d->route_f.begin(), d->route_f.end(), factor);
+    std::copy(d->route_b.begin(), d->route_b.end(), backward);
+    return 0;
 }
 
 MfView mf_view(const MfDevice* d) { return MfView{d->k, d->r, d->parent, d->rmap, d->L_off, d->rmap_off, d->L}; }

@@ -43,6 +43,11 @@ uint32_t* mf_epoch_ptr(const MfDevice* d);
 // factor, backward); null (the default) turns them off.
 void mf_debug_set_stamps(MfDevice* d, unsigned long long* stamps);
 constexpr int32_t kMfStall = 1 << 30;
+// Diagnostics (bos_debug_solver_routes): the route (bos_host.h BOS_ROUTE_F_* / BOS_ROUTE_B_*) every
+// front took, as the launch sites of mf_factor / mf_solve noted it when program 0's (and, sharded,
+// program 1's) sequence was first enqueued; -1 until both have been enqueued once. factor /
+// backward: one entry per supernode.
+int mf_debug_routes(const MfDevice* d, int8_t* factor, int8_t* backward);
 // work-queue tickets (kMfTickets ints, then kMfTickets exit counters); every flow launch leaves its
 // ticket zero (the last wave out resets it)
 int32_t* mf_tickets_ptr(const MfDevice* d);

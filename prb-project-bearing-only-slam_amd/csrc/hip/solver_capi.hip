@@ -2004,6 +2004,25 @@ int bos_debug_solver_stamps(bos_solver* s, int64_t capacity, uint64_t* stamps, i
     return BOS_OK;
 }
 
+int bos_debug_solver_routes(bos_solver* s, int64_t capacity, int32_t* routes, int32_t* nsuper) {
+    if (!s) return fail(BOS_ERR_INVALID, "null handle");
+    if (!uses_mf(s)) return fail(BOS_ERR_UNSUPPORTED, "multifrontal handles only");
+    const bos::Multifrontal& F = s->plan.mf;
+    if (nsuper) *nsuper = F.nsuper;
+    if (!routes && capacity == 0 && nsuper) return BOS_OK;
+    if (!routes || capacity < 4 * (int64_t)F.nsuper) return fail(BOS_ERR_INVALID, "routes: capacity 4 * supernodes");
+    std::vector<int8_t> rf(F.nsuper), rb(F.nsuper);
+    if (bos::dev::mf_debug_routes(s->mf, rf.data(), rb.data()))
+        return fail(BOS_ERR_INVALID, "routes: no step has been enqueued on this handle yet");
+    for (int x = 0; x < F.nsuper; ++x) {
+        routes[4 * x] = rf[x];
+        routes[4 * x + 1] = rb[x];
+        routes[4 * x + 2] = F.k[x];
+        routes[4 * x + 3] = F.r[x];
+    }
+    return BOS_OK;
+}
+
 int bos_debug_set_step_graph(bos_solver* s, int32_t enable) {
     if (!s) return fail(BOS_ERR_INVALID, "null handle");
     drop_graph(s);

@@ -162,3 +162,127 @@ def lin_parity(P, precision=bos.BOS_FP64, kt=1.0, damping=0.01, tol=1e-12, p999=
         assert abs(st["chi2"] - lin.chi2) <= 1e-3 * max(lin.chi2, 1.0)
     S.close()
     return eh, eb
+
+
+class SolveReference:
+    """H_nf x = b of one exported system, solved to (nearly) working precision of np.longdouble.
+    Vectors are in the reduced numbering: the reference dofs `idx` (the fixed pose's three removed)."""
+
+    def __init__(self, H, b, idx, x):
+        self.H, self.b, self.idx, self.x = H, b, idx, x
+        self._Hl, self._bl = H.astype(np.longdouble), b.astype(np.longdouble)
+        self._normH = float(np.abs(H).sum(axis=1).max())
+        self._unrefined = None
+
+    def fwd(self, x):
+        """Forward error ||x - x*||_inf / ||x*||_inf."""
+        return float(np.abs(np.asarray(x, dtype=np.longdouble) - self.x).max() / np.abs(self.x).max())
+
+    def eta(self, x):
+        """Normwise backward error ||b - H x||_inf / (||H||_inf ||x||_inf + ||b||_inf), residual in longdouble."""
+        xl = np.asarray(x, dtype=np.longdouble)
+        r = self._bl - self._Hl @ xl
+        return float(np.abs(r).max() / (self._normH * float(np.abs(xl).max()) + np.abs(self.b).max()))
+
+    def unrefined(self):
+        """(fwd, eta) of the two plain fp64 solvers the criterion measures its bound from, on this very
+        system: dense LAPACK Cholesky and SciPy SuperLU, neither refined."""
+        if self._unrefined is None:
+            import scipy.linalg as sla
+            import scipy.sparse.linalg as spla
+            xc = sla.cho_solve(sla.cho_factor(self.H, lower=True), self.b)
+            xs = spla.splu(sp.csc_matrix(self.H)).solve(self.b)
+            self._unrefined = {"chol": (self.fwd(xc), self.eta(xc)), "splu": (self.fwd(xs), self.eta(xs))}
+        return self._unrefined
+
+    def check(self, x, label=""):
+        """The solve criterion: fwd(x) <= 4 max(fwd_chol, fwd_splu) and eta(x) <= 8 max(eta_chol, eta_splu).
+        The bound comes from the two reference solvers on this system, never from x. Returns
+        (fwd, eta, fwd_bound / 4, eta_bound / 8, ok) and prints the four numbers."""
+        u = self.unrefined()
+        f_ref = max(u["chol"][0], u["splu"][0])
+        e_ref = max(u["chol"][1], u["splu"][1])
+        f, e = self.fwd(x), self.eta(x)
+        print(f"solve {label}: fwd {f:.3e} (ref max {f_ref:.3e}, ratio {f / f_ref:.3g}) "
+              f"eta {e:.3e} (ref max {e_ref:.3e}, ratio {e / e_ref:.3g})")
+        return f, e, f_ref, e_ref, bool(f <= 4 * f_ref and e <= 8 * e_ref)
+
+
+def solve_reference(rows, cols, vals, b, fixed, max_iter=60):
+    """x* of the exported system (bos_export_system: lower triangle of H_nf in reference dof numbering,
+    full b) with the fixed pose's dofs removed: dense LAPACK Cholesky, then iterative refinement with
+    the residual and the accumulated solution in np.longdouble until the correction is below 1e-18 of
+    ||x||_inf. Where cond(H) eps_longdouble lies above 1e-18 the corrections settle at that level
+    instead; the refinement then stops once a correction is no smaller than half the one before (x* is
+    still ~2^11 times finer than any fp64 solve of the system). Returns a SolveReference."""
+    import scipy.linalg as sla
+    N = len(b)
+    r64, c64 = np.asarray(rows, dtype=np.int64), np.asarray(cols, dtype=np.int64)
+    H = np.zeros((N, N))
+    np.add.at(H, (r64, c64), vals)
+    off = r64 != c64
+    np.add.at(H, (c64[off], r64[off]), np.asarray(vals)[off])
+    keep = np.ones(N, dtype=bool)
+    keep[3 * fixed:3 * fixed + 3] = False
+    idx = np.nonzero(keep)[0]
+    H = np.ascontiguousarray(H[np.ix_(idx, idx)])
+    bn = np.asarray(b, dtype=np.float64)[idx]
+    cf = sla.cho_factor(H, lower=True)
+    Hl, bl = H.astype(np.longdouble), bn.astype(np.longdouble)
+    x = sla.cho_solve(cf, bn).astype(np.longdouble)
+    last = np.inf
+    for _ in range(max_iter):
+        r = bl - Hl @ x
+        d = sla.cho_solve(cf, r.astype(np.float64)).astype(np.longdouble)
+        x = x + d
+        rel = float(np.abs(d).max() / np.abs(x).max())
+        if rel < 1e-18 or rel > 0.5 * last:
+            break
+        last = rel
+    return SolveReference(H, bn, idx, x)
+
+
+def joined_world(A, B, seed=9):
+    """Two worlds made one problem: B's poses and landmarks follow A's, and one odometry edge from A's
+    last pose to B's first (measured from the current estimates plus noise, the information of A's
+    first edge) ties B to A's fixed pose. The pose graph's only link between the two is that edge, so
+    a nested dissection cuts there and the two halves become sibling subtrees of different front sizes."""
+    rng = np.random.default_rng(seed)
+    s, d = A.NP - 1, A.NP
+    z = O.predict_odometry(A.pose_xyt[s], B.pose_xyt[0]) + rng.normal(0, 0.02, 3)
+    return bos.Problem(np.concatenate([A.pose_xyt, B.pose_xyt]), np.concatenate([A.lm_xy, B.lm_xy]),
+                       np.concatenate([A.b_pose, B.b_pose + A.NP]), np.concatenate([A.b_lm, B.b_lm + A.NL]),
+                       np.concatenate([A.b_z, B.b_z]), np.concatenate([A.o_src, B.o_src + A.NP, [s]]),
+                       np.concatenate([A.o_dst, B.o_dst + A.NP, [d]]), np.concatenate([A.o_z, B.o_z, z[None]]),
+                       np.concatenate([A.o_omega, B.o_omega, A.o_omega[:1]]), A.fixed)
+
+
+# The worlds of the solver route tests (tests/test_gpu_solver_routes.py, and the criterion's own CPU
+# test in tests/test_host.py): name -> (world, solver, schur_leaf). A world is the arguments of
+# bos.synthetic(..., seed=5), or two of them for joined_world. All with damping 0.01 (at damping 0 the
+# (65, 257, 8) world's H is singular: it has unobserved landmarks). DESIGN.md §5 has the routes each takes.
+SOLVER_WORLDS = {
+    "12_sn": ((12, 6, 3), bos.BOS_SOLVER_SUPERNODAL, 0),
+    "12_schur": ((12, 6, 3), bos.BOS_SOLVER_SCHUR, 0),
+    "40_schur_leaf40": ((40, 40, 4), bos.BOS_SOLVER_SCHUR, 40),
+    "65_schur_leaf80": ((65, 257, 8), bos.BOS_SOLVER_SCHUR, 80),
+    "200_schur": ((200, 300, 8), bos.BOS_SOLVER_SCHUR, 0),
+    "300_sn": ((300, 600, 10), bos.BOS_SOLVER_SUPERNODAL, 0),
+    "100_schur_leaf30": ((100, 100, 4), bos.BOS_SOLVER_SCHUR, 30),
+    "150_sn": ((150, 300, 20), bos.BOS_SOLVER_SUPERNODAL, 0),
+    "joined_schur_leaf80": (((45, 260, 12), (40, 40, 4)), bos.BOS_SOLVER_SCHUR, 80),
+}
+SOLVER_DAMPING = 0.01
+_solver_world_cache = {}
+
+
+def solver_world(name):
+    """(problem, solver, schur_leaf) of a SOLVER_WORLDS entry; the problem is built once."""
+    if name not in _solver_world_cache:
+        w, solver, leaf = SOLVER_WORLDS[name]
+        if isinstance(w[0], tuple):
+            P = joined_world(bos.synthetic(*w[0], seed=5), bos.synthetic(*w[1], seed=5))
+        else:
+            P = bos.synthetic(*w, seed=5)
+        _solver_world_cache[name] = (P, solver, leaf)
+    return _solver_world_cache[name]

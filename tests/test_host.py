@@ -12,7 +12,7 @@ import scipy.sparse.linalg as spla
 import bos
 import oracle as O
 from conftest import C1, MINI, ROOT
-from helpers import oracle_lower_nf, to_oracle
+from helpers import SOLVER_DAMPING, SOLVER_WORLDS, oracle_lower_nf, solve_reference, solver_world, to_oracle
 
 
 def _header_functions():
@@ -489,3 +489,31 @@ def test_cpu_baseline_matches_oracle(threads):
     from helpers import close_state
     ok, ep, el = close_state(pg, lg, po, lo)
     assert ok, (ep, el)
+
+
+@pytest.mark.parametrize("name", sorted(SOLVER_WORLDS))
+def test_solve_criterion_accepts_host_solve_and_rejects_a_corrupted_one(name):
+    """The criterion tests/test_gpu_solver_routes.py applies to the device solve, applied to the host
+    re-run of the device algorithm (plan_mf_selftest) on the oracle's system of every route world: it
+    passes; and it fails, against the uncorrupted system, when the largest off-diagonal stored value
+    of the input is scaled by 1 + 1e-6 (one update term slightly wrong)."""
+    P, solver, leaf = solver_world(name)
+    Q = to_oracle(P)
+    lin = O.linearize(Q, damping=SOLVER_DAMPING)
+    Hl = oracle_lower_nf(Q, lin)
+    coo = Hl.tocoo()
+    ref = solve_reference(coo.row, coo.col, coo.data, lin.b, P.fixed)
+    info = bos.plan_inspect(P, entries=True, solver=solver, schur_leaf=leaf)
+    vals = np.asarray(Hl.tocsr()[info["rows"], info["cols"]]).ravel()
+    perm = info["perm_to_ref"][:info["n"]]
+
+    def solve(v):
+        x = np.zeros(P.N)
+        x[perm] = bos.plan_mf_selftest(P, v, lin.b[perm], solver=solver, schur_leaf=leaf)
+        return x[ref.idx]
+
+    assert ref.check(solve(vals), f"{name} host")[-1]
+    off = np.nonzero(info["rows"] != info["cols"])[0]
+    bad = vals.copy()
+    bad[off[np.argmax(np.abs(vals[off]))]] *= 1 + 1e-6
+    assert not ref.check(solve(bad), f"{name} corrupted")[-1]
