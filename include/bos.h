@@ -274,6 +274,37 @@ int bos_get_last_dx(const struct bos_solver* s, double* dx);
  * handles (world_size > 1, a communicator, or external / direct exchange); BOS_ERR_DEVICE (with the
  * byte count in bos_last_error) when the pass's buffers cannot be allocated: the handle stays usable. */
 int bos_marginals(struct bos_solver* s, double* pose_cov, double* landmark_cov, int32_t* solver_info);
+/* Edge covariances of the current estimate: for every bearing and odometry edge of the problem, the
+ * cross-covariance block of its two nodes and the covariance of its predicted measurement, computed on
+ * the device in the same pass as the diagonal blocks of bos_marginals. H_nf, the damping, the kernel
+ * threshold, the state handling, the synchronous behaviour, *solver_info and the clearing of the pivot
+ * word are exactly those of bos_marginals; so are the "counts as a bos_linearize" rule and
+ * bos_get_last_dx afterwards. pose_cov and landmark_cov are bit for bit what bos_marginals returns at
+ * the same state. Host pointers, edge (measurement) order, row-major:
+ *   bearing_cross [M_b * 6]  Sigma(pose dofs, landmark dofs), 3 x 2
+ *   odom_cross    [M_o * 9]  Sigma(src dofs, dst dofs), 3 x 3
+ *   bearing_var   [M_b]      J Sigma_joint J^T, J the 1 x 5 bearing Jacobian
+ *   odom_cov      [M_o * 9]  J Sigma_joint J^T, J the 3 x 6 odometry Jacobian
+ * Any output may be NULL: it is neither downloaded nor computed (with all four edge outputs NULL the
+ * call is bos_marginals). Sigma_joint of an edge with nodes (a, b) is [[S_aa, S_ab], [S_ab^T, S_bb]].
+ * The fixed pose's diagonal block and every cross block that involves it are exactly zero: a bearing
+ * taken from the fixed pose has bearing_var = J_l S_ll J_l^T, an odometry edge that touches it uses the
+ * free pose's columns only. An odometry self-loop (src == dst) has odom_cross = S_aa and all four blocks
+ * of its Sigma_joint equal to S_aa. Duplicate edges each get their own slot, bit-identical between
+ * duplicates of one orientation; a reversed duplicate (dst, src) gets the transposed cross block.
+ * J is bearing_error_jacobian<double> / odometry_error_jacobian<double> (csrc/host/bos_math.hpp) at the
+ * fp64 master state with cos / sin computed in fp64, on every handle, fp32 ones included (as bos_cost);
+ * neither depends on the measurement. odom_cov is evaluated on its lower triangle and mirrored (each
+ * block is bit-symmetric), bearing_var is one fixed-order sum; two calls give identical bits.
+ * The cross blocks are pieces of the selected inverse the pass forms anyway (H lies inside L's
+ * pattern): each front writes those of its edges into a pair buffer, and one kernel projects every
+ * edge. The buffers are allocated at the first call that asks for an edge output; a handle that never
+ * does pays nothing.
+ * BOS_ERR_UNSUPPORTED on BOS_SOLVER_DENSE_CHOL / BOS_SOLVER_ROCSOLVER_RF handles and on sharded handles;
+ * BOS_ERR_DEVICE (with the byte count in bos_last_error) when the feature's buffers cannot be
+ * allocated: the handle stays usable and bos_marginals still works. */
+int bos_edge_covariances(struct bos_solver* s, double* bearing_cross, double* odom_cross, double* bearing_var,
+                         double* odom_cov, double* pose_cov, double* landmark_cov, int32_t* solver_info);
 /*
  * Levenberg-Marquardt with on-device step control (DESIGN.md §4 "Levenberg-Marquardt"). The objective is
  *   F(x) = sum over all edges of h(rho), rho = e^T Omega e, h(rho) = rho for rho <= kt and

@@ -105,6 +105,16 @@ int bos_plan_mf_selftest(const bos_problem* problem, const bos_options* options,
 int bos_plan_mf_marginals(const bos_problem* problem, const bos_options* options, const double* vals, double* pose_cov,
                           double* landmark_cov);
 
+/* Test hook: what bos_edge_covariances computes, in its literal host form: the host factorization and
+ * selected inverse of bos_plan_mf_marginals, every edge's cross block emitted through the plan's cross
+ * records (csrc/host/plan.hpp selinv_cross_records), and the projection J Sigma_joint J^T by the very
+ * code the device kernel runs (csrc/host/edge_cov.hpp), J evaluated at the problem's state
+ * (problem->pose_xyt, problem->landmark_xy: both required). Outputs as for bos_edge_covariances; any
+ * may be NULL. No device is used. */
+int bos_plan_mf_edge_covariances(const bos_problem* problem, const bos_options* options, const double* vals,
+                                 double* bearing_cross, double* odom_cross, double* bearing_var, double* odom_cov,
+                                 double* pose_cov, double* landmark_cov);
+
 /* Owner of every node (NP poses, then NL landmarks) when the multifrontal solve is sharded over
  * `world` ranks: the rank, -1 for the replicated top, -2 for the fixed pose. */
 int bos_plan_node_owner(const bos_problem* problem, const bos_options* options, int32_t world, int32_t* owner);
@@ -162,6 +172,11 @@ int bos_time_steps(struct bos_solver* s, int32_t n, double* ms_per_step);
  * blocks (host clock); *sigma_bytes (may be NULL) = bytes of the Sigma-front buffer (0 before the
  * first call). */
 int bos_marginals_timing(const struct bos_solver* s, double ms[4], int64_t* sigma_bytes);
+/* Measurement helper (tools/edge_cov_time.py): the last bos_edge_covariances call's split, ms[5] = J+H
+ * build, factorization, selected inverse with the cross blocks' emission, projection kernel (HIP
+ * events) and download of the outputs (host clock); *edge_bytes (may be NULL) = bytes of the feature's
+ * device buffers (0 before the first call). */
+int bos_edge_covariances_timing(const struct bos_solver* s, double ms[5], int64_t* edge_bytes);
 /* Measurement helper (tools/lm_time.py): n launches of bos_cost's kernel back to back between two
  * HIP events on the handle's stream: *ms_per_pass. */
 int bos_time_cost(struct bos_solver* s, int32_t n, double* ms_per_pass);

@@ -58,6 +58,7 @@ EXPORTED_SYMBOLS = [
     "bos_last_step_stamps", "bos_marginals", "bos_plan_mf_marginals", "bos_marginals_timing",
     "bos_lm_default_options", "bos_cost", "bos_optimize", "bos_time_cost", "bos_cpu_gn_set_kernel_threshold",
     "bos_cpu_gn_cost", "bos_cpu_gn_optimize", "bos_lm_rule_apply",
+    "bos_edge_covariances", "bos_plan_mf_edge_covariances", "bos_edge_covariances_timing",
 ]
 
 # bos_lm_result.reason
@@ -207,6 +208,10 @@ def lib():
         "bos_plan_mf_selftest": (ctypes.c_int, [ctypes.POINTER(bos_problem), ctypes.POINTER(bos_options), _dp, _dp, _dp]),
         "bos_plan_mf_marginals": (ctypes.c_int, [ctypes.POINTER(bos_problem), ctypes.POINTER(bos_options), _dp, _dp, _dp]),
         "bos_marginals": (ctypes.c_int, [vp, _dp, _dp, _ip]),
+        "bos_edge_covariances": (ctypes.c_int, [vp, _dp, _dp, _dp, _dp, _dp, _dp, _ip]),
+        "bos_plan_mf_edge_covariances": (ctypes.c_int, [ctypes.POINTER(bos_problem), ctypes.POINTER(bos_options), _dp, _dp, _dp,
+                                                         _dp, _dp, _dp, _dp]),
+        "bos_edge_covariances_timing": (ctypes.c_int, [vp, _dp, ctypes.POINTER(ctypes.c_int64)]),
         "bos_marginals_timing": (ctypes.c_int, [vp, _dp, ctypes.POINTER(ctypes.c_int64)]),
         "bos_lm_default_options": (None, [ctypes.POINTER(bos_lm_options)]),
         "bos_cost": (ctypes.c_int, [vp, _dp, _dp, _ip]),
@@ -489,6 +494,34 @@ def plan_mf_marginals(P: Problem, vals, solver: int = BOS_SOLVER_SCHUR, schur_le
     _check(lib().bos_plan_mf_marginals(ctypes.byref(cs), ctypes.byref(opt), _ptr(v, ctypes.c_double),
                                        _ptr(pose, ctypes.c_double), _ptr(lm, ctypes.c_double)), "plan_mf_marginals")
     return pose, lm
+
+
+def _edge_cov_arrays(P: Problem, cross: bool, projected: bool, blocks: bool) -> dict:
+    """The output arrays of an edge-covariance call; None where not asked for."""
+    Mb, Mo = len(P.b_z), len(P.o_z)
+    return {"bearing_cross": np.zeros((Mb, 3, 2)) if cross else None,
+            "odom_cross": np.zeros((Mo, 3, 3)) if cross else None,
+            "bearing_var": np.zeros(Mb) if projected else None,
+            "odom_cov": np.zeros((Mo, 3, 3)) if projected else None,
+            "pose_cov": np.zeros((P.NP, 3, 3)) if blocks else None,
+            "landmark_cov": np.zeros((P.NL, 2, 2)) if blocks else None}
+
+
+_EDGE_COV_ORDER = ("bearing_cross", "odom_cross", "bearing_var", "odom_cov", "pose_cov", "landmark_cov")
+
+
+def plan_mf_edge_covariances(P: Problem, vals, solver: int = BOS_SOLVER_SCHUR, schur_leaf: int = 0):
+    """Host form of Solver.edge_covariances() (test hook, bos_plan_mf_edge_covariances): the host
+    selected inverse of the H_nf whose stored entries are vals, the edges' cross blocks through the
+    plan's cross records and the projection at P's state. Returns the dict of arrays (no solver_info)."""
+    cs = P.c_struct()
+    v = np.ascontiguousarray(vals, dtype=np.float64)
+    out = _edge_cov_arrays(P, True, True, True)
+    opt = options(solver, schur_leaf=schur_leaf)
+    _check(lib().bos_plan_mf_edge_covariances(ctypes.byref(cs), ctypes.byref(opt), _ptr(v, ctypes.c_double),
+                                              *[_ptr(out[k], ctypes.c_double) for k in _EDGE_COV_ORDER]),
+           "plan_mf_edge_covariances")
+    return out
 
 
 def plan_shard_selftest(P: Problem, world: int, vals, rhs, solver: int = BOS_SOLVER_SCHUR):
@@ -833,6 +866,28 @@ class Solver:
         _check(lib().bos_marginals(self._h, _ptr(pose, ctypes.c_double), _ptr(lm, ctypes.c_double),
                                    ctypes.byref(info)), "bos_marginals")
         return pose, lm, info.value
+
+    def edge_covariances(self, cross: bool = True, projected: bool = True, blocks: bool = True) -> dict:
+        """Edge covariances of the current estimate (bos_edge_covariances): a dict with bearing_cross
+        [Mb, 3, 2] and odom_cross [Mo, 3, 3] (cross), bearing_var [Mb] and odom_cov [Mo, 3, 3]
+        (projected), pose_cov [NP, 3, 3] and landmark_cov [NL, 2, 2] (blocks), and solver_info; outputs
+        that were not asked for are None."""
+        out = _edge_cov_arrays(self.P, cross, projected, blocks)
+        info = ctypes.c_int32(0)
+        _check(lib().bos_edge_covariances(self._h, *[_ptr(out[k], ctypes.c_double) for k in _EDGE_COV_ORDER],
+                                          ctypes.byref(info)), "bos_edge_covariances")
+        out["solver_info"] = info.value
+        return out
+
+    def edge_covariances_timing(self) -> dict:
+        """The last edge_covariances() call's split in ms and the feature's device bytes
+        (bos_edge_covariances_timing)."""
+        ms = np.zeros(5)
+        nb = ctypes.c_int64(0)
+        _check(lib().bos_edge_covariances_timing(self._h, _ptr(ms, ctypes.c_double), ctypes.byref(nb)),
+               "bos_edge_covariances_timing")
+        return {"jh_ms": ms[0], "factor_ms": ms[1], "selinv_ms": ms[2], "project_ms": ms[3], "download_ms": ms[4],
+                "edge_bytes": nb.value}
 
     def cost(self) -> dict:
         """The objective F at the current state, the plain chi2 and the count of edges beyond the

@@ -16,12 +16,19 @@
 // fronts of up to kMfBlkMaxM rows (one wavefront for m <= kMfWaveMaxM, else 256 threads and up to
 // 128 KiB, requested as mf_factor_blk does); larger fronts, or 65-128-row fronts when that LDS is not
 // granted, keep Li, Z and S_RJ in a global workspace and read G from the parent's front in place.
+//
+// Edge covariances: the cross block of an edge's two nodes is a piece of S_RJ (or of S_JJ when both
+// nodes share the supernode) of the front that owns the node eliminated first. The X = true
+// instantiation of the kernel writes those pieces, through the plan's cross records, into the pair
+// buffer, in all three front classes (S_RJ sits in LDS or in the workspace behind the same pointer);
+// the X = false instantiation is the marginals' kernel, unchanged.
 #include "selinv.hpp"
 
 #include <algorithm>
 #include <vector>
 
 #include "../host/plan.hpp"
+#include "edge_cov.hpp"
 #include "multifrontal.hpp"
 
 namespace bos {
@@ -36,13 +43,15 @@ struct SelArgs {
     const double* L;
     double *S, *ws, *out;
     int64_t lm_base;          // the landmark blocks' offset in out (9 NP)
+    const int32_t *cr_ptr, *cr_rec;   // cross records (plan.hpp CrossRecords), read by selinv_front<T, true> only
+    double* pairs;                    // [9 n_pairs]
 };
 
 constexpr int kWaveThreads = 64, kBlkThreads = 256;
 constexpr int kDefaultLds = 64 * 1024;
 typedef double dbl4 __attribute__((ext_vector_type(4)));
 
-template <int T> __global__ __launch_bounds__(T) void selinv_front(const SelArgs a) {
+template <int T, bool X> __global__ __launch_bounds__(T) void selinv_front(const SelArgs a) {
     extern __shared__ double sel_lds[];
     const int s = a.list[blockIdx.x], t = threadIdx.x;
     const int k = a.k[s], r = a.r[s], m = k + r;
@@ -155,6 +164,16 @@ template <int T> __global__ __launch_bounds__(T) void selinv_front(const SelArgs
         const int x = xy / sz, y = xy % sz;
         a.out[(sz == 3 ? 0 : a.lm_base) + rec[1] + xy] = sjj(loc + x, loc + y);
     }
+    if constexpr (X) {   // the edges' cross blocks: entry xy of the pair's block, canonical orientation
+        const int c0 = a.cr_ptr[s], nc = a.cr_ptr[s + 1] - c0;
+        for (int e = t; e < nc * 9; e += T) {
+            const int32_t* rec = a.cr_rec + kCrossRec * (int64_t)(c0 + e / 9);
+            const int pos = rec[0], loc = rec[1], rows = rec[2], cols = rec[3], xy = e % 9;
+            if (xy >= rows * cols) continue;
+            const int i = rec[5] ? xy % rows : xy / cols, j = rec[5] ? xy / rows : xy % cols;
+            a.pairs[9 * (int64_t)rec[4] + xy] = pos >= k ? SR[(pos - k + i) + (loc + j) * r] : sjj(pos + i, loc + j);
+        }
+    }
 }
 
 struct Launch {
@@ -170,7 +189,18 @@ template <typename X> bool put(X** p, const std::vector<X>& v, int64_t& bytes) {
 
 }  // namespace
 
+// the feature's state (mf_edge_cov_build): index arrays, pair buffer and per-edge outputs in one arena
+struct EdgeCovDev {
+    char* arena = nullptr;
+    int64_t bytes = 0, n_pairs = 0;
+    int Mb = 0, Mo = 0;
+    int32_t *cr_ptr = nullptr, *cr_rec = nullptr, *edge_slot = nullptr, *edge_tr = nullptr;
+    int32_t *b_pose = nullptr, *b_lm = nullptr, *o_src = nullptr, *o_dst = nullptr;
+    double *pairs = nullptr, *bearing_cross = nullptr, *odom_cross = nullptr, *bearing_var = nullptr, *odom_cov = nullptr;
+};
+
 struct SelInv {
+    EdgeCovDev ec;
     std::vector<Launch> launches;
     int32_t *list = nullptr, *out_ptr = nullptr, *out_rec = nullptr;
     int64_t *S_off = nullptr, *ws_off = nullptr;
@@ -183,6 +213,7 @@ void selinv_destroy(SelInv* p) {
     void* bufs[] = {p->list, p->out_ptr, p->out_rec, p->S_off, p->ws_off, p->S, p->ws, p->out};
     for (void* b : bufs)
         if (b) (void)hipFree(b);
+    if (p->ec.arena) (void)hipFree(p->ec.arena);
     delete p;
 }
 
@@ -204,7 +235,9 @@ int selinv_build(const Plan& P, SelInv** out, std::string& err) {
     }
     // 65-128-row fronts keep their m m doubles in LDS when the workgroup kernel may take them
     const int blk_lds = kMfBlkMaxM * kMfBlkMaxM * (int)sizeof(double);
-    const bool big_lds = hipFuncSetAttribute((const void*)selinv_front<kBlkThreads>, hipFuncAttributeMaxDynamicSharedMemorySize,
+    const bool big_lds = hipFuncSetAttribute((const void*)selinv_front<kBlkThreads, false>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                             blk_lds) == hipSuccess &&
+                         hipFuncSetAttribute((const void*)selinv_front<kBlkThreads, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                              blk_lds) == hipSuccess;
     (void)hipGetLastError();
     const int lds_cap = big_lds ? blk_lds : kDefaultLds;
@@ -281,15 +314,18 @@ int selinv_build(const Plan& P, SelInv** out, std::string& err) {
 
 }  // namespace
 
-int mf_selected_inverse(MfDevice* d, const Plan& P, const double** out_dev, hipStream_t s, std::string& err) {
+int mf_selected_inverse(MfDevice* d, const Plan& P, const double** out_dev, hipStream_t s, std::string& err, bool emit_cross) {
     SelInv** slot = mf_selinv_slot(d);
     if (!*slot) {
         const int rc = selinv_build(P, slot, err);
         if (rc) { *slot = nullptr; return rc; }
     }
     SelInv* si = *slot;
+    if (emit_cross && !si->ec.arena) { err = "edge covariances: the cross records are not built"; return -1; }
     const MfView v = mf_view(d);
     SelArgs a;
+    a.cr_ptr = emit_cross ? si->ec.cr_ptr : nullptr; a.cr_rec = emit_cross ? si->ec.cr_rec : nullptr;
+    a.pairs = emit_cross ? si->ec.pairs : nullptr;
     a.k = v.k; a.r = v.r; a.parent = v.parent; a.rmap = v.rmap; a.L_off = v.L_off; a.rmap_off = v.rmap_off; a.L = v.L;
     a.out_ptr = si->out_ptr; a.out_rec = si->out_rec; a.S_off = si->S_off; a.ws_off = si->ws_off;
     a.S = si->S; a.ws = si->ws; a.out = si->out; a.lm_base = si->lm_base;
@@ -297,12 +333,121 @@ int mf_selected_inverse(MfDevice* d, const Plan& P, const double** out_dev, hipS
     for (size_t i = 0; i < si->launches.size() && e == hipSuccess; ++i) {
         const Launch& ln = si->launches[i];
         a.list = si->list + ln.first;
-        if (ln.threads == kWaveThreads) selinv_front<kWaveThreads><<<ln.count, kWaveThreads, ln.lds, s>>>(a);
-        else selinv_front<kBlkThreads><<<ln.count, kBlkThreads, ln.lds, s>>>(a);
+        if (ln.threads == kWaveThreads) {
+            if (emit_cross) selinv_front<kWaveThreads, true><<<ln.count, kWaveThreads, ln.lds, s>>>(a);
+            else selinv_front<kWaveThreads, false><<<ln.count, kWaveThreads, ln.lds, s>>>(a);
+        } else {
+            if (emit_cross) selinv_front<kBlkThreads, true><<<ln.count, kBlkThreads, ln.lds, s>>>(a);
+            else selinv_front<kBlkThreads, false><<<ln.count, kBlkThreads, ln.lds, s>>>(a);
+        }
         e = hipGetLastError();
     }
     if (e != hipSuccess) { err = std::string("marginals: selected-inverse launch: ") + hipGetErrorString(e); return -2; }
     *out_dev = si->out;
+    return 0;
+}
+
+bool mf_edge_cov_built(const MfDevice* d) {
+    SelInv* const* slot = mf_selinv_slot(const_cast<MfDevice*>(d));
+    return *slot && (*slot)->ec.arena;
+}
+
+int64_t mf_edge_cov_bytes(const MfDevice* d) {
+    SelInv* const* slot = mf_selinv_slot(const_cast<MfDevice*>(d));
+    return *slot ? (*slot)->ec.bytes : 0;
+}
+
+int mf_edge_cov_build(MfDevice* d, const Plan& P, const EdgeList& E, std::string& err) {
+    SelInv** slot = mf_selinv_slot(d);
+    if (!*slot) {
+        const int rc = selinv_build(P, slot, err);
+        if (rc) { *slot = nullptr; return rc; }
+    }
+    EdgeCovDev& ec = (*slot)->ec;
+    if (ec.arena) return 0;
+    const Multifrontal& F = P.mf;
+    CrossRecords cr;
+    if (!selinv_cross_records(P, E.Mb, E.Mo, E.b_pose, E.b_lm, E.o_src, E.o_dst, cr)) {
+        err = "bos_edge_covariances: an edge's cross block is not inside one front";
+        return -1;
+    }
+    // everything the kernels index with, checked once (the edges' endpoints: selinv_cross_records)
+    const int64_t edges = (int64_t)E.Mb + E.Mo, nrec = cr.ptr[F.nsuper];
+    bool good = nrec == cr.n_pairs && (int64_t)cr.rec.size() == kCrossRec * nrec && (int64_t)cr.edge_slot.size() == edges &&
+                (int64_t)cr.edge_tr.size() == edges;
+    for (int s = 0; s < F.nsuper && good; ++s)
+        for (int q = cr.ptr[s]; q < cr.ptr[s + 1] && good; ++q) {
+            const int32_t* rec = cr.rec.data() + (size_t)kCrossRec * q;
+            const bool pose_pair = rec[2] == 3 && rec[3] == 3;
+            good = rec[0] >= 0 && rec[0] + rec[2] <= F.k[s] + F.r[s] && rec[1] >= 0 && rec[1] + rec[3] <= F.k[s] &&
+                   (pose_pair || rec[2] * rec[3] == 6) && rec[4] >= 0 && rec[4] < cr.n_pairs && (rec[5] == 0 || rec[5] == 1);
+        }
+    for (int64_t e = 0; e < edges && good; ++e) good = cr.edge_slot[e] >= -1 && cr.edge_slot[e] < cr.n_pairs;
+    if (!good) { err = "bos_edge_covariances: malformed cross records"; return -1; }
+
+    // one arena: [index arrays | pair buffer | per-edge outputs], every part aligned to 256 bytes
+    int64_t bytes = 0;
+    auto take = [&](int64_t count, int64_t elem) {
+        const int64_t off = bytes;
+        bytes += (std::max<int64_t>(count, 1) * elem + 255) / 256 * 256;
+        return off;
+    };
+    const int64_t o_ptr = take((int64_t)cr.ptr.size(), 4), o_rec = take((int64_t)cr.rec.size(), 4), o_slot = take(edges, 4),
+                  o_tr = take(edges, 4), o_bp = take(E.Mb, 4), o_bl = take(E.Mb, 4), o_os = take(E.Mo, 4), o_od = take(E.Mo, 4),
+                  o_pairs = take(9 * cr.n_pairs, 8), o_bc = take(6 * (int64_t)E.Mb, 8), o_oc = take(9 * (int64_t)E.Mo, 8),
+                  o_bv = take(E.Mb, 8), o_ov = take(9 * (int64_t)E.Mo, 8);
+    char* arena = nullptr;
+    if (hipMalloc((void**)&arena, (size_t)bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        err = "bos_edge_covariances: device allocation of " + std::to_string(bytes) + " bytes failed";
+        return -2;
+    }
+    auto up = [&](int64_t off, const int32_t* src, int64_t count) {
+        return count == 0 || hipMemcpy(arena + off, src, (size_t)count * sizeof(int32_t), hipMemcpyHostToDevice) == hipSuccess;
+    };
+    if (!(up(o_ptr, cr.ptr.data(), (int64_t)cr.ptr.size()) && up(o_rec, cr.rec.data(), (int64_t)cr.rec.size()) &&
+          up(o_slot, cr.edge_slot.data(), edges) && up(o_tr, cr.edge_tr.data(), edges) && up(o_bp, E.b_pose, E.Mb) &&
+          up(o_bl, E.b_lm, E.Mb) && up(o_os, E.o_src, E.Mo) && up(o_od, E.o_dst, E.Mo))) {
+        (void)hipGetLastError();
+        (void)hipFree(arena);
+        err = "bos_edge_covariances: upload of the cross records failed";
+        return -2;
+    }
+    ec.arena = arena;
+    ec.bytes = bytes;
+    ec.n_pairs = cr.n_pairs;
+    ec.Mb = E.Mb; ec.Mo = E.Mo;
+    ec.cr_ptr = (int32_t*)(arena + o_ptr); ec.cr_rec = (int32_t*)(arena + o_rec);
+    ec.edge_slot = (int32_t*)(arena + o_slot); ec.edge_tr = (int32_t*)(arena + o_tr);
+    ec.b_pose = (int32_t*)(arena + o_bp); ec.b_lm = (int32_t*)(arena + o_bl);
+    ec.o_src = (int32_t*)(arena + o_os); ec.o_dst = (int32_t*)(arena + o_od);
+    ec.pairs = (double*)(arena + o_pairs);
+    ec.bearing_cross = (double*)(arena + o_bc); ec.odom_cross = (double*)(arena + o_oc);
+    ec.bearing_var = (double*)(arena + o_bv); ec.odom_cov = (double*)(arena + o_ov);
+    return 0;
+}
+
+int mf_edge_project(MfDevice* d, const double* pose, const double* lm, const bool want[4], EdgeCovResult* res, hipStream_t s,
+                    std::string& err) {
+    SelInv** slot = mf_selinv_slot(d);
+    if (!*slot || !(*slot)->ec.arena) { err = "edge covariances: the cross records are not built"; return -1; }
+    const SelInv* si = *slot;
+    const EdgeCovDev& ec = si->ec;
+    EdgeCovIn in;
+    in.Mb = ec.Mb; in.Mo = ec.Mo;
+    in.pose = pose; in.lm = lm;
+    in.pose_cov = si->out; in.lm_cov = si->out + si->lm_base;
+    in.pairs = ec.pairs;
+    in.b_pose = ec.b_pose; in.b_lm = ec.b_lm; in.o_src = ec.o_src; in.o_dst = ec.o_dst;
+    in.edge_slot = ec.edge_slot; in.edge_tr = ec.edge_tr;
+    EdgeCovOut o;
+    o.bearing_cross = want[0] ? ec.bearing_cross : nullptr;
+    o.odom_cross = want[1] ? ec.odom_cross : nullptr;
+    o.bearing_var = want[2] ? ec.bearing_var : nullptr;
+    o.odom_cov = want[3] ? ec.odom_cov : nullptr;
+    const hipError_t e = launch_edge_project(in, o, s);
+    if (e != hipSuccess) { err = std::string("edge covariances: projection launch: ") + hipGetErrorString(e); return -2; }
+    res->bearing_cross = o.bearing_cross; res->odom_cross = o.odom_cross; res->bearing_var = o.bearing_var; res->odom_cov = o.odom_cov;
     return 0;
 }
 

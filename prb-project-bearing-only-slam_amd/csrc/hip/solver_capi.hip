@@ -203,6 +203,8 @@ struct bos_solver {
     int32_t seq_seen = 0, seq_pending = 0;
     // the last bos_marginals: J+H, factorization, selected inverse (events), download (host clock)
     double marg_ms[4] = {};
+    // the last bos_edge_covariances: the same, the projection kernel (events) before the download
+    double edge_ms[5] = {};
     // ---- bos_cost / bos_optimize (hip/lm.hpp). The fp64 originals of what the cost pass reads and the
     // J+H keeps only in T: odometry z / information (upper triangle) and the bearing weights (has_w)
     std::vector<double> h_oz, h_oom, h_bw;
@@ -2178,20 +2180,64 @@ int bos_last_step_stamps(const bos_solver* s, uint64_t stamps[8]) {
     return BOS_OK;
 }
 
-int bos_marginals(bos_solver* s, double* pose_cov, double* landmark_cov, int32_t* solver_info) {
+}  // extern "C"
+
+namespace {
+
+// The feature's device state at the first bos_edge_covariances (hip/selinv.hip mf_edge_cov_build): the
+// edges in measurement order come back from the device copies the handle already keeps (the
+// triangulation's CSR by landmark, the odometry's endpoints)
+int edge_cov_setup(bos_solver* s) {
+    if (bos::dev::mf_edge_cov_built(s->mf)) return BOS_OK;
+    std::vector<int32_t> bp(s->Mb, 0), bl(s->Mb, 0), os(s->Mo, 0), od(s->Mo, 0);
+    if (s->Mb) {
+        std::vector<int32_t> tptr(s->NL + 1), tobs(s->Mb);
+        HIP_TRY(hipMemcpy(tptr.data(), s->tri_ptr, tptr.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(tobs.data(), s->tri_obs, tobs.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(bp.data(), s->tri_pose, bp.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+        for (int l = 0; l < s->NL; ++l)
+            for (int q = tptr[l]; q < tptr[l + 1]; ++q) bl[tobs[q]] = l;
+    }
+    if (s->Mo) {
+        HIP_TRY(hipMemcpy(os.data(), s->o_src, os.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(od.data(), s->o_dst, od.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+    }
+    bos::dev::EdgeList E;
+    E.Mb = s->Mb; E.Mo = s->Mo;
+    E.b_pose = bp.data(); E.b_lm = bl.data(); E.o_src = os.data(); E.o_dst = od.data();
+    std::string err;
+    const int rc = bos::dev::mf_edge_cov_build(s->mf, s->plan, E, err);
+    if (rc) return fail(rc == -1 ? BOS_ERR_UNSUPPORTED : BOS_ERR_DEVICE, err);
+    return BOS_OK;
+}
+
+// bos_marginals (edge = nullptr) and bos_edge_covariances (edge[4] = bearing_cross, odom_cross,
+// bearing_var, odom_cov; with all four null the pass is the marginals' own)
+int covariance_pass(bos_solver* s, const char* name, double* const* edge, double* pose_cov, double* landmark_cov,
+                    int32_t* solver_info) {
     if (!s) return fail(BOS_ERR_INVALID, "null handle");
     if (!uses_mf(s))
-        return fail(BOS_ERR_UNSUPPORTED, "bos_marginals needs a multifrontal solver (BOS_SOLVER_SCHUR or BOS_SOLVER_SUPERNODAL)");
+        return fail(BOS_ERR_UNSUPPORTED, std::string(name) + " needs a multifrontal solver (BOS_SOLVER_SCHUR or BOS_SOLVER_SUPERNODAL)");
     if (s->sharded || s->obs || s->world > 1 || s->comm || s->external || s->p2p)
-        return fail(BOS_ERR_UNSUPPORTED, "bos_marginals on a sharded handle (a rank holds part of the factor)");
+        return fail(BOS_ERR_UNSUPPORTED, std::string(name) + " on a sharded handle (a rank holds part of the factor)");
     HIP_TRY(hipSetDevice(s->device));
     if (solver_info) *solver_info = 0;
     const int64_t n = s->plan.n;
     const size_t np9 = 9 * (size_t)s->NP, nl4 = 4 * (size_t)s->NL;
-    if (n == 0) {
+    const size_t ecount[4] = {6 * (size_t)s->Mb, 9 * (size_t)s->Mo, (size_t)s->Mb, 9 * (size_t)s->Mo};
+    bool want[4] = {false, false, false, false};
+    bool any_edge = false;
+    for (int i = 0; i < 4 && edge; ++i) any_edge |= want[i] = edge[i] != nullptr && ecount[i] > 0;
+    if (n == 0) {   // the fixed pose alone: every block and every cross block is zero
         if (pose_cov) std::fill(pose_cov, pose_cov + np9, 0.0);
         if (landmark_cov) std::fill(landmark_cov, landmark_cov + nl4, 0.0);
+        for (int i = 0; i < 4; ++i)
+            if (want[i]) std::fill(edge[i], edge[i] + ecount[i], 0.0);
         return BOS_OK;
+    }
+    if (any_edge) {
+        const int rc = edge_cov_setup(s);
+        if (rc) return rc;
     }
     // bos_step returns on its status word, before the stream has drained: everything below is
     // ordered after it by the stream
@@ -2205,10 +2251,15 @@ int bos_marginals(bos_solver* s, double* pose_cov, double* landmark_cov, int32_t
     HIP_TRY(hipEventRecord(s->ev[2], s->stream));
     const double* out = nullptr;
     std::string err;
-    const int src = bos::dev::mf_selected_inverse(s->mf, s->plan, &out, s->stream, err);
+    int src = bos::dev::mf_selected_inverse(s->mf, s->plan, &out, s->stream, err, any_edge);
     // the factorization's word, read and cleared whatever happened next: a step expects it zero
     int32_t info = 0;
     hipError_t e = hipEventRecord(s->ev[3], s->stream);
+    bos::dev::EdgeCovResult er;
+    if (any_edge && !src && e == hipSuccess) {
+        src = bos::dev::mf_edge_project(s->mf, s->d_pose, s->d_lm, want, &er, s->stream, err);
+        e = hipEventRecord(s->ev[4], s->stream);
+    }
     if (e == hipSuccess) e = hipMemcpyAsync(&info, bos::dev::mf_info_ptr(s->mf), sizeof(info), hipMemcpyDeviceToHost, s->stream);
     if (e == hipSuccess) e = hipMemsetAsync(bos::dev::mf_info_ptr(s->mf), 0, sizeof(int32_t), s->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
@@ -2219,9 +2270,42 @@ int bos_marginals(bos_solver* s, double* pose_cov, double* landmark_cov, int32_t
     const auto t0 = std::chrono::steady_clock::now();
     if (pose_cov) HIP_TRY(hipMemcpy(pose_cov, out, np9 * sizeof(double), hipMemcpyDeviceToHost));
     if (landmark_cov && nl4) HIP_TRY(hipMemcpy(landmark_cov, out + np9, nl4 * sizeof(double), hipMemcpyDeviceToHost));
-    s->marg_ms[3] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    for (int i = 0; i < 3; ++i) s->marg_ms[i] = elapsed(s->ev[i], s->ev[i + 1]);
+    if (any_edge) {
+        const double* dev[4] = {er.bearing_cross, er.odom_cross, er.bearing_var, er.odom_cov};
+        for (int i = 0; i < 4; ++i)
+            if (want[i]) HIP_TRY(hipMemcpy(edge[i], dev[i], ecount[i] * sizeof(double), hipMemcpyDeviceToHost));
+    }
+    const double dl = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    if (edge) {
+        for (int i = 0; i < 3; ++i) s->edge_ms[i] = elapsed(s->ev[i], s->ev[i + 1]);
+        s->edge_ms[3] = any_edge ? elapsed(s->ev[3], s->ev[4]) : 0.0;
+        s->edge_ms[4] = dl;
+    } else {
+        s->marg_ms[3] = dl;
+        for (int i = 0; i < 3; ++i) s->marg_ms[i] = elapsed(s->ev[i], s->ev[i + 1]);
+    }
     if (solver_info) *solver_info = info;
+    return BOS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int bos_marginals(bos_solver* s, double* pose_cov, double* landmark_cov, int32_t* solver_info) {
+    return covariance_pass(s, "bos_marginals", nullptr, pose_cov, landmark_cov, solver_info);
+}
+
+int bos_edge_covariances(bos_solver* s, double* bearing_cross, double* odom_cross, double* bearing_var, double* odom_cov,
+                         double* pose_cov, double* landmark_cov, int32_t* solver_info) {
+    double* const edge[4] = {bearing_cross, odom_cross, bearing_var, odom_cov};
+    return covariance_pass(s, "bos_edge_covariances", edge, pose_cov, landmark_cov, solver_info);
+}
+
+int bos_edge_covariances_timing(const bos_solver* s, double ms[5], int64_t* edge_bytes) {
+    if (!s || !ms) return fail(BOS_ERR_INVALID, "null argument");
+    for (int i = 0; i < 5; ++i) ms[i] = s->edge_ms[i];
+    if (edge_bytes) *edge_bytes = s->mf ? bos::dev::mf_edge_cov_bytes(s->mf) : 0;
     return BOS_OK;
 }
 

@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../../include/bos_host.h"
+#include "edge_cov.hpp"
 #include "g2o_utils.hpp"
 #include "host_mf.hpp"
 #include "plan.hpp"
@@ -408,6 +409,50 @@ int bos_plan_mf_marginals(const bos_problem* pb, const bos_options* options, con
     double none = 0.0;
     if (!M.selected_inverse(pose_cov, landmark_cov ? landmark_cov : &none))
         return hfail(BOS_ERR_INVALID, "a node's dofs are split between two supernodes");
+    return BOS_OK;
+}
+
+// Test hook: bos_edge_covariances in its literal host form: the host factorization and selected inverse
+// with the cross records' emission (plan.hpp selinv_cross_records), then the per-edge projection of
+// edge_cov.hpp at the problem's state (theta wrapped as bos_create wraps it).
+int bos_plan_mf_edge_covariances(const bos_problem* pb, const bos_options* options, const double* vals, double* bearing_cross,
+                                 double* odom_cross, double* bearing_var, double* odom_cov, double* pose_cov,
+                                 double* landmark_cov) {
+    if (!pb || !vals || !pb->pose_xyt || (!pb->landmark_xy && pb->num_landmarks > 0)) return hfail(BOS_ERR_INVALID, "null argument");
+    bos::ProblemIndex pi;
+    bos_options opt;
+    int fmode = 0;
+    int rc = plan_args(pb, options, pi, fmode, opt);
+    if (rc) return rc;
+    if (opt.solver != BOS_SOLVER_SUPERNODAL && opt.solver != BOS_SOLVER_SCHUR)
+        return hfail(BOS_ERR_INVALID, "edge covariances need a multifrontal solver");
+    bos::Plan P;
+    std::string err;
+    rc = bos::build_plan(pi, 0, 1, fmode, P, err);
+    if (rc) return hfail(rc, err);
+    bos::CrossRecords cr;
+    if (!bos::selinv_cross_records(P, pi.Mb, pi.Mo, pi.b_pose, pi.b_lm, pi.o_src, pi.o_dst, cr))
+        return hfail(BOS_ERR_UNSUPPORTED, "bos_edge_covariances: an edge's cross block is not inside one front");
+    const std::vector<double> rhs(P.n, 0.0);
+    bos::HostMf M(P, vals, rhs.data());
+    M.factor([](int) { return true; });
+    std::vector<double> pc(9 * (size_t)P.NP + 1), lc(4 * (size_t)P.NL + 1), pairs(9 * (size_t)cr.n_pairs + 1, 0.0);
+    if (!M.selected_inverse(pc.data(), lc.data(), &cr, pairs.data()))
+        return hfail(BOS_ERR_UNSUPPORTED, "a node's dofs are split between two supernodes");
+    std::vector<double> pose(pb->pose_xyt, pb->pose_xyt + 3 * (size_t)P.NP);
+    for (int i = 0; i < P.NP; ++i) pose[3 * i + 2] = bos::normalized_angle<double>(bos::smallest_angle<double>(pose[3 * i + 2]));
+    bos::EdgeCovIn in;
+    in.Mb = pi.Mb; in.Mo = pi.Mo;
+    in.pose = pose.data(); in.lm = pb->landmark_xy;
+    in.pose_cov = pc.data(); in.lm_cov = lc.data(); in.pairs = pairs.data();
+    in.b_pose = pi.b_pose; in.b_lm = pi.b_lm; in.o_src = pi.o_src; in.o_dst = pi.o_dst;
+    in.edge_slot = cr.edge_slot.data(); in.edge_tr = cr.edge_tr.data();
+    bos::EdgeCovOut o;
+    o.bearing_cross = bearing_cross; o.odom_cross = odom_cross; o.bearing_var = bearing_var; o.odom_cov = odom_cov;
+    for (int64_t e = 0; e < pi.Mb; ++e) bos::edge_cov_bearing(in, o, e);
+    for (int64_t e = 0; e < pi.Mo; ++e) bos::edge_cov_odometry(in, o, e);
+    if (pose_cov) std::copy(pc.begin(), pc.end() - 1, pose_cov);
+    if (landmark_cov) std::copy(lc.begin(), lc.end() - 1, landmark_cov);
     return BOS_OK;
 }
 

@@ -254,7 +254,7 @@ struct HostMf {
     std::vector<std::vector<double>> sig;
 
     void selinv_front(int s, double* pose_cov, double* lm_cov, const std::vector<int32_t>& out_ptr,
-                      const std::vector<int32_t>& out_rec) {
+                      const std::vector<int32_t>& out_rec, const CrossRecords* cross = nullptr, double* pairs = nullptr) {
         const int k = F.k[s], r = F.r[s], m = k + r, p = F.parent[s];
         const double* Ls = L.data() + F.L_off[s];
         // G = Sigma_RR from the parent's front through rmap
@@ -313,20 +313,30 @@ struct HostMf {
             for (int a = 0; a < sz; ++a)
                 for (int b = 0; b < sz; ++b) o[a * sz + b] = J[(loc + a) + (size_t)(loc + b) * k];
         }
+        if (!cross) return;
+        for (int q = cross->ptr[s]; q < cross->ptr[s + 1]; ++q) {   // the edges' cross blocks (plan.hpp CrossRecords)
+            const int32_t* rec = cross->rec.data() + (size_t)kCrossRec * q;
+            const int pos = rec[0], loc = rec[1], rows = rec[2], cols = rec[3];
+            for (int xy = 0; xy < rows * cols; ++xy) {
+                const int i = rec[5] ? xy % rows : xy / cols, j = rec[5] ? xy / rows : xy % cols;
+                pairs[9 * (size_t)rec[4] + xy] = pos >= k ? S[(pos - k + i) + (size_t)(loc + j) * r] : J[(pos + i) + (size_t)(loc + j) * k];
+            }
+        }
     }
 
     // pose_cov [NP * 9], lm_cov [NL * 4] (row-major, stix order; the fixed pose's block zero); L holds
-    // the factor (factor() has run). Returns false when a node straddles two supernodes.
-    bool selected_inverse(double* pose_cov, double* lm_cov) {
+    // the factor (factor() has run). Returns false when a node straddles two supernodes. With cross
+    // records, pairs [9 n_pairs] receives every pair's cross block as well.
+    bool selected_inverse(double* pose_cov, double* lm_cov, const CrossRecords* cross = nullptr, double* pairs = nullptr) {
         std::vector<int32_t> out_ptr, out_rec;
         if (!selinv_records(P, out_ptr, out_rec)) return false;
         std::fill(pose_cov, pose_cov + 9 * (size_t)P.NP, 0.0);
         std::fill(lm_cov, lm_cov + 4 * (size_t)P.NL, 0.0);
         sig.assign(F.nsuper, {});
         auto all = [](int) { return true; };
-        each_level(true, all, [&](int s) { selinv_front(s, pose_cov, lm_cov, out_ptr, out_rec); });
+        each_level(true, all, [&](int s) { selinv_front(s, pose_cov, lm_cov, out_ptr, out_rec, cross, pairs); });
         const std::vector<int32_t>& folds = F.fold_list;
-        auto body = [&](int64_t j) { selinv_front(folds[j], pose_cov, lm_cov, out_ptr, out_rec); };
+        auto body = [&](int64_t j) { selinv_front(folds[j], pose_cov, lm_cov, out_ptr, out_rec, cross, pairs); };
         if (pool) pool->parallel_for((int64_t)folds.size(), body);
         else
             for (size_t j = 0; j < folds.size(); ++j) body((int64_t)j);

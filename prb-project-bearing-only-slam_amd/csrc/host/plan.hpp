@@ -10,8 +10,10 @@
 // Nodes: pose stix u in [0, NP) (3 dofs), landmark stix l as node NP + l (2 dofs).
 #pragma once
 
+#include <algorithm>
 #include <cstdint>
 #include <string>
+#include <utility>
 #include <vector>
 
 namespace bos {
@@ -268,6 +270,97 @@ inline bool selinv_records(const Plan& P, std::vector<int32_t>& out_ptr, std::ve
         out_rec[3 * q + 1] = u < P.NP ? 9 * u : 4 * (u - P.NP);
         out_rec[3 * q + 2] = u < P.NP ? 3 : 2;
     }
+    return true;
+}
+
+// Edge covariances (HostMf::selected_inverse, hip/selinv.hip, hip/edge_cov.hip): where the cross block
+// of every edge's two nodes sits in the recursion. The edges are reduced to unique unordered node
+// pairs in a canonical orientation: (pose, landmark) for bearings, slots allocated landmark-major,
+// then (lower stix, higher stix) for pose pairs, a self-loop being the pair (a, a); pairs with the
+// fixed pose have no slot. Slot q owns pairs[9 q ...]: the block Sigma(first node, second node)
+// row-major (3 x 2: 6 values; 3 x 3: 9). The pair's node eliminated first (u, smaller node_pos) lies
+// in a supernode s whose front also holds the other node (v): H is inside L's pattern. One record per
+// pair, kCrossRec ints: (v's first row in s's front: < k inside S_JJ, else a row of S_RJ; u's first dof
+// inside s's k own dofs; v's dofs; u's dofs; the slot; 1 when u is the canonical first node, so that the
+// front's (row of v, column of u) entry is the block's transposed one), grouped per supernode in CSR
+// form and sorted by slot inside each.
+// edge_slot / edge_tr [Mb + Mo] (bearings, then odometry): the edge's slot (-1: it involves the fixed
+// pose) and 1 when the edge runs against the canonical orientation (src stix > dst stix).
+constexpr int kCrossRec = 6;
+struct CrossRecords {
+    int64_t n_pairs = 0;
+    std::vector<int32_t> ptr, rec, edge_slot, edge_tr;
+};
+// False when a node's dofs are split between supernodes, or the other node's rows are not found as
+// consecutive entries of the front; everything a kernel indexes with is checked here.
+inline bool selinv_cross_records(const Plan& P, int Mb, int Mo, const int32_t* b_pose, const int32_t* b_lm,
+                                 const int32_t* o_src, const int32_t* o_dst, CrossRecords& out) {
+    const Multifrontal& F = P.mf;
+    typedef std::pair<int32_t, int32_t> Pair;
+    std::vector<Pair> bp, pp;   // (landmark, pose) and (lower pose, higher pose)
+    for (int e = 0; e < Mb; ++e) {
+        if (b_pose[e] < 0 || b_pose[e] >= P.NP || b_lm[e] < 0 || b_lm[e] >= P.NL) return false;
+        if (b_pose[e] != P.fixed) bp.emplace_back(b_lm[e], b_pose[e]);
+    }
+    for (int e = 0; e < Mo; ++e) {
+        if (o_src[e] < 0 || o_src[e] >= P.NP || o_dst[e] < 0 || o_dst[e] >= P.NP) return false;
+        if (o_src[e] != P.fixed && o_dst[e] != P.fixed) pp.emplace_back(std::min(o_src[e], o_dst[e]), std::max(o_src[e], o_dst[e]));
+    }
+    auto uniq = [](std::vector<Pair>& v) {
+        std::sort(v.begin(), v.end());
+        v.erase(std::unique(v.begin(), v.end()), v.end());
+    };
+    uniq(bp);
+    uniq(pp);
+    const int64_t nb = (int64_t)bp.size(), np = (int64_t)pp.size();
+    if (nb + np > INT32_MAX / 9) return false;
+    out.n_pairs = nb + np;
+    out.edge_slot.assign((size_t)Mb + Mo, -1);
+    out.edge_tr.assign((size_t)Mb + Mo, 0);
+    for (int e = 0; e < Mb; ++e)
+        if (b_pose[e] != P.fixed)
+            out.edge_slot[e] = (int32_t)(std::lower_bound(bp.begin(), bp.end(), Pair(b_lm[e], b_pose[e])) - bp.begin());
+    for (int e = 0; e < Mo; ++e) {
+        const int a = o_src[e], b = o_dst[e];
+        if (a == P.fixed || b == P.fixed) continue;
+        out.edge_slot[Mb + e] = (int32_t)(nb + (std::lower_bound(pp.begin(), pp.end(), Pair(std::min(a, b), std::max(a, b))) - pp.begin()));
+        out.edge_tr[Mb + e] = a > b ? 1 : 0;
+    }
+    std::vector<int32_t> sn_of(P.n, -1);
+    for (int s = 0; s < F.nsuper; ++s)
+        for (int i = 0; i < F.k[s]; ++i) sn_of[F.col0[s] + i] = s;
+    std::vector<int32_t> rec((size_t)kCrossRec * out.n_pairs), sn(out.n_pairs);
+    for (int64_t q = 0; q < out.n_pairs; ++q) {
+        // canonical first and second node
+        const int a = q < nb ? bp[q].second : pp[q - nb].first, b = q < nb ? P.NP + bp[q].first : pp[q - nb].second;
+        const bool a_first = P.node_pos[a] <= P.node_pos[b];
+        const int u = a_first ? a : b, v = a_first ? b : a;
+        const int szu = u < P.NP ? 3 : 2, szv = v < P.NP ? 3 : 2, du = P.node_dof[u], dv = P.node_dof[v];
+        if (du < 0 || du + szu > P.n || dv < 0 || dv + szv > P.n) return false;
+        const int s = sn_of[du];
+        if (s < 0 || sn_of[du + szu - 1] != s) return false;
+        const int k = F.k[s], m = k + F.r[s];
+        const int32_t* fi = F.findex.data() + F.findex_off[s];
+        int pos = -1;
+        if (dv >= F.col0[s] && dv < F.col0[s] + k) pos = dv - F.col0[s];
+        else
+            for (int i = k; i < m; ++i)
+                if (fi[i] == dv) { pos = i; break; }
+        if (pos < 0 || pos + szv > m) return false;
+        for (int i = 0; i < szv; ++i)
+            if (fi[pos + i] != dv + i) return false;
+        int32_t* o = rec.data() + (size_t)kCrossRec * q;
+        o[0] = pos; o[1] = du - F.col0[s]; o[2] = szv; o[3] = szu; o[4] = (int32_t)q; o[5] = (u == a && u != v) ? 1 : 0;
+        if (o[1] < 0 || o[1] + szu > k) return false;
+        sn[q] = s;
+    }
+    out.ptr.assign(F.nsuper + 1, 0);
+    for (int64_t q = 0; q < out.n_pairs; ++q) ++out.ptr[sn[q] + 1];
+    for (int s = 0; s < F.nsuper; ++s) out.ptr[s + 1] += out.ptr[s];
+    out.rec.assign(rec.size(), 0);
+    std::vector<int32_t> fill(out.ptr.begin(), out.ptr.end() - 1);
+    for (int64_t q = 0; q < out.n_pairs; ++q)   // slot order: a supernode's records stay sorted by slot
+        std::copy(rec.begin() + kCrossRec * q, rec.begin() + kCrossRec * (q + 1), out.rec.begin() + (size_t)kCrossRec * fill[sn[q]]++);
     return true;
 }
 
