@@ -115,6 +115,18 @@ int bos_plan_mf_edge_covariances(const bos_problem* problem, const bos_options* 
                                  double* bearing_cross, double* odom_cross, double* bearing_var, double* odom_cov,
                                  double* pose_cov, double* landmark_cov);
 
+/* The fronts of the plan's multifrontal tree, from the plan alone (no values, no device):
+ * fronts[BOS_PLAN_FRONT_COLS * nsuper] = per supernode: k (own dofs), r (update rows), tree level
+ * (leaves 0; -1 for a folded landmark, which is in no level), parent (-1 for a root), children
+ * (folded ones included), folded children, 1 when the supernode itself is folded, and the selected
+ * inverse's records of the front (csrc/host/plan.hpp selinv_records / selinv_cross_records): whole
+ * nodes (diagonal blocks), cross records that read S_RJ, cross records that evaluate S_JJ, and how
+ * many of either are transposed. fronts NULL with capacity 0: only *nsuper is returned. options as
+ * for bos_plan_mf_selftest. */
+enum { BOS_PLAN_FRONT_COLS = 11 };
+int bos_plan_mf_fronts(const bos_problem* problem, const bos_options* options, int64_t capacity, int32_t* fronts,
+                       int32_t* nsuper);
+
 /* Owner of every node (NP poses, then NL landmarks) when the multifrontal solve is sharded over
  * `world` ranks: the rank, -1 for the replicated top, -2 for the fixed pose. */
 int bos_plan_node_owner(const bos_problem* problem, const bos_options* options, int32_t world, int32_t* owner);
@@ -249,6 +261,31 @@ enum {
  * BOS_ERR_INVALID before the handle's first bos_step (the sequence has not been enqueued yet) or
  * when capacity < 4 * nsuper. */
 int bos_debug_solver_routes(struct bos_solver* s, int64_t capacity, int32_t* routes, int32_t* nsuper);
+
+/* Diagnostics: what the selected inverse's launch plan (hip/selinv.hip selinv_build) decided for every
+ * front, from the plan this handle built at its first bos_marginals / bos_edge_covariances call. The
+ * class is noted where selinv_build chooses the front's thread count and its workspace slice; nothing
+ * is launched or changed by the call. */
+enum {
+    BOS_SELINV_WAVE_LDS = 0,       /* one wavefront, the working set in LDS (m <= 64; folded landmarks too) */
+    BOS_SELINV_BLK_LDS_MFMA = 1,   /* 256 threads, the working set in LDS, G Z on f64 MFMA tiles (65-128)  */
+    BOS_SELINV_BLK_WORKSPACE = 2,  /* 256 threads, Li / Z / S_RJ in the global workspace, G read in place   */
+    BOS_SELINV_CLASS_COUNT = 3
+};
+enum { BOS_SELINV_COLS = 10 };
+/* fronts[BOS_SELINV_COLS * nsuper] = per front, in the plan's supernode order: class, index of its
+ * launch in the pass, k, r, 1 when it is a folded landmark (in fold_list), 1 when it stores a Sigma
+ * front for its children, its diagonal-block records (whole nodes), and, once the cross records exist
+ * (after the first bos_edge_covariances; -1 before), its cross records that read S_RJ, those that
+ * evaluate S_JJ, and how many of either are transposed. node_front[NP + NL] (may be NULL) = the front
+ * whose records write each node's block (poses, then landmarks; -1 for the fixed pose); edge_front
+ * [Mb + Mo] (may be NULL) = the front whose cross record emits each edge's cross block (bearings, then
+ * odometry; -1 when the edge involves the fixed pose or the cross records do not exist yet). fronts
+ * NULL with capacity 0: only *nsuper is returned. BOS_ERR_UNSUPPORTED for a handle without the
+ * multifrontal solver, BOS_ERR_INVALID before the first bos_marginals / bos_edge_covariances call or when
+ * capacity < BOS_SELINV_COLS * nsuper. */
+int bos_debug_selinv_fronts(struct bos_solver* s, int64_t capacity, int32_t* fronts, int32_t* nsuper, int32_t* node_front,
+                            int32_t* edge_front);
 
 /* Diagnostics: one J+H launch with per-wave timeline stamps, 8 x uint64 per wave: block, wave in
  * block, kind (0 pose lanes / 1 landmark lanes), t_start, t_loop, t_loop_end, t_end (realtime clock,

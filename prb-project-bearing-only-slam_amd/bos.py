@@ -51,7 +51,7 @@ EXPORTED_SYMBOLS = [
     "bos_plan_node_owner", "bos_step_phase", "bos_exchange_size", "bos_exchange_download", "bos_exchange_upload",
     "bos_node_owner",
     "bos_debug_set_g2o_parser", "bos_debug_inject_stall", "bos_debug_set_step_graph", "bos_debug_solver_stamps",
-    "bos_debug_solver_routes",
+    "bos_debug_solver_routes", "bos_debug_selinv_fronts", "bos_plan_mf_fronts",
     "bos_time_linearize", "bos_time_triangulate", "bos_time_steps", "bos_cpu_gn_create", "bos_cpu_gn_step", "bos_cpu_gn_get_state",
     "bos_cpu_gn_destroy", "bos_normalized_angle_f64", "bos_normalized_angle_f32", "bos_exchange_p2p_handle",
     "bos_exchange_p2p_connect", "bos_time_facade_steps", "bos_debug_facade_selftest", "bos_set_exchange_timeout",
@@ -237,6 +237,8 @@ def lib():
         "bos_debug_inject_stall": (ctypes.c_int, [vp]),
         "bos_debug_set_step_graph": (ctypes.c_int, [vp, ctypes.c_int32]),
         "bos_debug_solver_routes": (ctypes.c_int, [vp, ctypes.c_int64, _ip, _ip]),
+        "bos_debug_selinv_fronts": (ctypes.c_int, [vp, ctypes.c_int64, _ip, _ip, _ip, _ip]),
+        "bos_plan_mf_fronts": (ctypes.c_int, [ctypes.POINTER(bos_problem), ctypes.POINTER(bos_options), ctypes.c_int64, _ip, _ip]),
         "bos_debug_solver_stamps": (ctypes.c_int, [vp, ctypes.c_int64, ctypes.POINTER(ctypes.c_uint64),
                                                    ctypes.POINTER(ctypes.c_int32)]),
         "bos_time_linearize": (ctypes.c_int, [vp, ctypes.c_int32, ctypes.c_int32, _dp]),
@@ -524,6 +526,26 @@ def plan_mf_edge_covariances(P: Problem, vals, solver: int = BOS_SOLVER_SCHUR, s
     return out
 
 
+# columns of plan_mf_fronts (bos_host.h BOS_PLAN_FRONT_COLS)
+PLAN_FRONT_COLS = ("k", "r", "level", "parent", "children", "folded_children", "folded", "diag_records", "cross_rj",
+                   "cross_jj", "cross_transposed")
+
+
+def plan_mf_fronts(P: Problem, solver: int = BOS_SOLVER_SCHUR, schur_leaf: int = 0) -> np.ndarray:
+    """The fronts of the plan's multifrontal tree, host only (bos_plan_mf_fronts): [nsuper, 11] int32
+    with the columns PLAN_FRONT_COLS: k, r, tree level (-1: a folded landmark), parent (-1: a root),
+    children, folded children, 1 when the supernode itself is folded, and the selected inverse's records
+    of the front: whole nodes, cross records reading S_RJ, evaluating S_JJ, and the transposed ones."""
+    cs = P.c_struct()
+    opt = options(solver, schur_leaf=schur_leaf)
+    n = ctypes.c_int32(0)
+    _check(lib().bos_plan_mf_fronts(ctypes.byref(cs), ctypes.byref(opt), 0, None, ctypes.byref(n)), "plan_mf_fronts")
+    out = np.zeros((n.value, len(PLAN_FRONT_COLS)), dtype=np.int32)
+    _check(lib().bos_plan_mf_fronts(ctypes.byref(cs), ctypes.byref(opt), out.size, _ptr(out, ctypes.c_int32),
+                                    ctypes.byref(n)), "plan_mf_fronts")
+    return out
+
+
 def plan_shard_selftest(P: Problem, world: int, vals, rhs, solver: int = BOS_SOLVER_SCHUR):
     """Host simulation of the sharded solve over `world` ranks, exchanges included (test hook):
     raises unless the merged solution equals the one-rank solution bit for bit and every rank's J+H
@@ -808,6 +830,29 @@ class Solver:
         _check(lib().bos_debug_solver_routes(self._h, out.size, _ptr(out, ctypes.c_int32), ctypes.byref(n)),
                "bos_debug_solver_routes")
         return out
+
+    # bos_host.h BOS_SELINV_*, by value, and the columns of debug_selinv_fronts()["fronts"]
+    SELINV_CLASSES = ("wave_lds", "blk_lds_mfma", "blk_workspace")
+    SELINV_COLS = ("class", "launch", "k", "r", "folded", "sigma_front", "diag_records", "cross_rj", "cross_jj",
+                   "cross_transposed")
+
+    def debug_selinv_fronts(self) -> dict:
+        """Diagnostics: what the selected inverse's launch plan decided (bos_host.h
+        bos_debug_selinv_fronts; BosError before the handle's first marginals() / edge_covariances()).
+        "fronts": [nsuper, 10] int32 with the columns SELINV_COLS (class = SELINV_CLASSES index; the
+        three cross columns are -1 until edge_covariances() has built the cross records);
+        "node_front": [NP + NL] the front that writes each node's block (-1: the fixed pose);
+        "edge_front": [Mb + Mo] the front that emits each edge's cross block (bearings, then odometry;
+        -1: the edge involves the fixed pose, or no cross records yet)."""
+        n = ctypes.c_int32(0)
+        _check(lib().bos_debug_selinv_fronts(self._h, 0, None, ctypes.byref(n), None, None), "bos_debug_selinv_fronts")
+        fronts = np.zeros((n.value, len(self.SELINV_COLS)), dtype=np.int32)
+        node = np.zeros(self.P.NP + self.P.NL, dtype=np.int32)
+        edge = np.zeros(len(self.P.b_z) + len(self.P.o_z), dtype=np.int32)
+        _check(lib().bos_debug_selinv_fronts(self._h, fronts.size, _ptr(fronts, ctypes.c_int32), ctypes.byref(n),
+                                             _ptr(node, ctypes.c_int32), _ptr(edge, ctypes.c_int32)),
+               "bos_debug_selinv_fronts")
+        return {"fronts": fronts, "node_front": node, "edge_front": edge}
 
     def debug_set_step_graph(self, enable: bool):
         """Test hook: GN steps as individual launches (False) or the captured graph (True, default)."""

@@ -27,6 +27,7 @@
 #include <algorithm>
 #include <vector>
 
+#include "../../../include/bos_host.h"
 #include "../host/plan.hpp"
 #include "edge_cov.hpp"
 #include "multifrontal.hpp"
@@ -197,11 +198,17 @@ struct EdgeCovDev {
     int32_t *cr_ptr = nullptr, *cr_rec = nullptr, *edge_slot = nullptr, *edge_tr = nullptr;
     int32_t *b_pose = nullptr, *b_lm = nullptr, *o_src = nullptr, *o_dst = nullptr;
     double *pairs = nullptr, *bearing_cross = nullptr, *odom_cross = nullptr, *bearing_var = nullptr, *odom_cov = nullptr;
+    CrossRecords h_cr;   // the host's copy of what was uploaded (mf_selinv_report)
 };
 
 struct SelInv {
     EdgeCovDev ec;
     std::vector<Launch> launches;
+    // the report (mf_selinv_report): per supernode the class and the launch selinv_build's add gave it,
+    // and the host's copies of the diagonal-block records and the Sigma fronts' offsets
+    std::vector<int8_t> cls;
+    std::vector<int32_t> launch_of, h_out_ptr, h_out_rec;
+    std::vector<int64_t> h_S_off;
     int32_t *list = nullptr, *out_ptr = nullptr, *out_rec = nullptr;
     int64_t *S_off = nullptr, *ws_off = nullptr;
     double *S = nullptr, *ws = nullptr, *out = nullptr;
@@ -243,6 +250,8 @@ int selinv_build(const Plan& P, SelInv** out, std::string& err) {
     const int lds_cap = big_lds ? blk_lds : kDefaultLds;
 
     SelInv* si = new SelInv();
+    si->cls.assign(F.nsuper, (int8_t)-1);
+    si->launch_of.assign(F.nsuper, -1);
     std::vector<int32_t> list;
     std::vector<int64_t> S_off(F.nsuper, -1), ws_off(F.nsuper, -1);
     int64_t S_size = 0, ws_size = 0;
@@ -266,10 +275,13 @@ int selinv_build(const Plan& P, SelInv** out, std::string& err) {
             const int64_t k = F.k[s], r = F.r[s], m = k + r, bytes = m * m * (int64_t)sizeof(double);
             if (bytes <= (threads == kWaveThreads ? kDefaultLds : lds_cap)) {
                 ln.lds = std::max<int>(ln.lds, (int)bytes);
+                si->cls[s] = threads == kWaveThreads ? BOS_SELINV_WAVE_LDS : BOS_SELINV_BLK_LDS_MFMA;
             } else {
                 ws_off[s] = ws;   // launches follow each other on one stream: they share the workspace
                 ws += k * k + 2 * r * k;
+                si->cls[s] = BOS_SELINV_BLK_WORKSPACE;
             }
+            si->launch_of[s] = (int32_t)si->launches.size();
             list.push_back(s);
         }
         ws_size = std::max(ws_size, ws);
@@ -301,6 +313,9 @@ int selinv_build(const Plan& P, SelInv** out, std::string& err) {
     if (ok) { bytes = si->sigma_bytes; ok = hipMalloc((void**)&si->S, bytes) == hipSuccess; if (!ok) si->S = nullptr; }
     if (ok) { bytes = std::max<int64_t>(ws_size, 1) * (int64_t)sizeof(double); ok = hipMalloc((void**)&si->ws, bytes) == hipSuccess; if (!ok) si->ws = nullptr; }
     if (ok) { bytes = std::max<int64_t>(si->out_count, 1) * (int64_t)sizeof(double); ok = hipMalloc((void**)&si->out, bytes) == hipSuccess; if (!ok) si->out = nullptr; }
+    si->h_out_ptr.swap(out_ptr);
+    si->h_out_rec.swap(out_rec);
+    si->h_S_off.swap(S_off);
     if (!ok) {
         (void)hipGetLastError();
         err = "marginals: device allocation of " + std::to_string(bytes) + " bytes failed (Sigma-front buffer: " +
@@ -424,6 +439,42 @@ int mf_edge_cov_build(MfDevice* d, const Plan& P, const EdgeList& E, std::string
     ec.pairs = (double*)(arena + o_pairs);
     ec.bearing_cross = (double*)(arena + o_bc); ec.odom_cross = (double*)(arena + o_oc);
     ec.bearing_var = (double*)(arena + o_bv); ec.odom_cov = (double*)(arena + o_ov);
+    ec.h_cr = std::move(cr);
+    return 0;
+}
+
+int mf_selinv_report(const MfDevice* d, const Plan& P, int32_t* fronts, int32_t* node_front, int32_t* edge_front) {
+    SelInv* const* slot = mf_selinv_slot(const_cast<MfDevice*>(d));
+    if (!*slot) return -1;
+    const SelInv* si = *slot;
+    const Multifrontal& F = P.mf;
+    const bool cross = si->ec.arena != nullptr;
+    const CrossRecords& cr = si->ec.h_cr;
+    std::vector<char> folded(F.nsuper, 0);
+    for (int s : F.fold_list) folded[s] = 1;
+    if (node_front) std::fill(node_front, node_front + P.NP + P.NL, -1);
+    std::vector<int32_t> slot_front(cross ? cr.n_pairs : 0, -1);
+    for (int s = 0; s < F.nsuper; ++s) {
+        int32_t* o = fronts + (size_t)BOS_SELINV_COLS * s;
+        o[0] = si->cls[s]; o[1] = si->launch_of[s]; o[2] = F.k[s]; o[3] = F.r[s]; o[4] = folded[s];
+        o[5] = si->h_S_off[s] >= 0;
+        o[6] = si->h_out_ptr[s + 1] - si->h_out_ptr[s];
+        o[7] = o[8] = o[9] = cross ? 0 : -1;
+        if (node_front)
+            for (int q = si->h_out_ptr[s]; q < si->h_out_ptr[s + 1]; ++q) {
+                const int32_t* rec = si->h_out_rec.data() + 3 * (size_t)q;
+                node_front[rec[2] == 3 ? rec[1] / 9 : P.NP + rec[1] / 4] = s;
+            }
+        for (int q = cross ? cr.ptr[s] : 0; cross && q < cr.ptr[s + 1]; ++q) {
+            const int32_t* rec = cr.rec.data() + (size_t)kCrossRec * q;
+            ++o[rec[0] >= F.k[s] ? 7 : 8];
+            o[9] += rec[5];
+            slot_front[rec[4]] = s;
+        }
+    }
+    if (edge_front)
+        for (int64_t e = 0; e < (int64_t)P.Mb + P.Mo; ++e)
+            edge_front[e] = cross && cr.edge_slot[e] >= 0 ? slot_front[cr.edge_slot[e]] : -1;
     return 0;
 }
 

@@ -50,6 +50,10 @@ int mf_edge_project(MfDevice* d, const double* pose, const double* lm, const boo
 int64_t mf_edge_cov_bytes(const MfDevice* d);
 // bytes of the Sigma-front buffer (0 before the first call)
 int64_t mf_selinv_sigma_bytes(const MfDevice* d);
+// Diagnostics (bos_debug_selinv_fronts, whose layout this fills): fronts [BOS_SELINV_COLS nsuper],
+// node_front [NP + NL] and edge_front [Mb + Mo] (either may be null), from what selinv_build noted and
+// the host's copies of the records. -1 before the state is built; nothing is launched.
+int mf_selinv_report(const MfDevice* d, const Plan& P, int32_t* fronts, int32_t* node_front, int32_t* edge_front);
 void selinv_destroy(SelInv* p);
 
 }  // namespace dev

@@ -2025,6 +2025,20 @@ int bos_debug_solver_routes(bos_solver* s, int64_t capacity, int32_t* routes, in
     return BOS_OK;
 }
 
+int bos_debug_selinv_fronts(bos_solver* s, int64_t capacity, int32_t* fronts, int32_t* nsuper, int32_t* node_front,
+                            int32_t* edge_front) {
+    if (!s) return fail(BOS_ERR_INVALID, "null handle");
+    if (!uses_mf(s)) return fail(BOS_ERR_UNSUPPORTED, "multifrontal handles only");
+    const bos::Multifrontal& F = s->plan.mf;
+    if (nsuper) *nsuper = F.nsuper;
+    if (!fronts && capacity == 0 && nsuper) return BOS_OK;
+    if (!fronts || capacity < (int64_t)BOS_SELINV_COLS * F.nsuper)
+        return fail(BOS_ERR_INVALID, "selinv fronts: capacity BOS_SELINV_COLS * supernodes");
+    if (bos::dev::mf_selinv_report(s->mf, s->plan, fronts, node_front, edge_front))
+        return fail(BOS_ERR_INVALID, "selinv fronts: no bos_marginals / bos_edge_covariances call has built the plan on this handle yet");
+    return BOS_OK;
+}
+
 int bos_debug_set_step_graph(bos_solver* s, int32_t enable) {
     if (!s) return fail(BOS_ERR_INVALID, "null handle");
     drop_graph(s);

@@ -360,6 +360,50 @@ int bos_plan_node_owner(const bos_problem* pb, const bos_options* options, int32
     return BOS_OK;
 }
 
+// The fronts of the plan's tree (bos_host.h BOS_PLAN_FRONT_COLS): shapes, levels and links only.
+int bos_plan_mf_fronts(const bos_problem* pb, const bos_options* options, int64_t capacity, int32_t* fronts, int32_t* nsuper) {
+    if (!pb || (!fronts && !nsuper)) return hfail(BOS_ERR_INVALID, "null argument");
+    bos::ProblemIndex pi;
+    bos_options opt;
+    int fmode = 0;
+    int rc = plan_args(pb, options, pi, fmode, opt);
+    if (rc) return rc;
+    if (opt.solver != BOS_SOLVER_SUPERNODAL && opt.solver != BOS_SOLVER_SCHUR)
+        return hfail(BOS_ERR_INVALID, "the fronts need a multifrontal solver");
+    bos::Plan P;
+    std::string err;
+    rc = bos::build_plan(pi, 0, 1, fmode, P, err);
+    if (rc) return hfail(rc, err);
+    const bos::Multifrontal& F = P.mf;
+    if (nsuper) *nsuper = F.nsuper;
+    if (!fronts && capacity == 0) return BOS_OK;
+    if (!fronts || capacity < (int64_t)BOS_PLAN_FRONT_COLS * F.nsuper) return hfail(BOS_ERR_INVALID, "fronts: capacity BOS_PLAN_FRONT_COLS * supernodes");
+    std::vector<int32_t> lev(F.nsuper, -1), folded(F.nsuper, 0);
+    for (int l = 0; l < F.nlevels; ++l)
+        for (int q = F.level_ptr[l]; q < F.level_ptr[l + 1]; ++q) lev[F.level[q]] = l;
+    for (int32_t x : F.fold_list) folded[x] = 1;
+    std::vector<int32_t> out_ptr, out_rec;
+    bos::CrossRecords cr;
+    if (!bos::selinv_records(P, out_ptr, out_rec) ||
+        !bos::selinv_cross_records(P, pi.Mb, pi.Mo, pi.b_pose, pi.b_lm, pi.o_src, pi.o_dst, cr))
+        return hfail(BOS_ERR_UNSUPPORTED, "a node or an edge's cross block is not inside one front");
+    for (int x = 0; x < F.nsuper; ++x) {
+        int32_t* o = fronts + (size_t)BOS_PLAN_FRONT_COLS * x;
+        o[0] = F.k[x]; o[1] = F.r[x]; o[2] = lev[x]; o[3] = F.parent[x];
+        o[4] = F.child_ptr[x + 1] - F.child_ptr[x];
+        o[5] = F.fold_cnt.empty() ? 0 : F.fold_cnt[x];
+        o[6] = folded[x];
+        o[7] = out_ptr[x + 1] - out_ptr[x];
+        o[8] = o[9] = o[10] = 0;
+        for (int q = cr.ptr[x]; q < cr.ptr[x + 1]; ++q) {
+            const int32_t* rec = cr.rec.data() + (size_t)bos::kCrossRec * q;
+            ++o[rec[0] >= F.k[x] ? 8 : 9];
+            o[10] += rec[5];
+        }
+    }
+    return BOS_OK;
+}
+
 // Test hook: runs the multifrontal algorithm of hip/multifrontal.hip on the host with the plan's
 // tree and maps (validates the symbolic structure without a GPU). vals: values of the stored
 // entries of H_nf in bos_plan_inspect's order (scattered into the block array here), rhs / x:

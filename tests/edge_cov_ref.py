@@ -12,10 +12,14 @@ Error of a projected entry (u, v): |out - ref| / (s_u s_v), s_u = sum_i |J_ui| s
 sd_i = sqrt(Sigma_ref[i, i]), <= 2 tol: every entry of Sigma_joint is off by at most tol sd_i sd_j, so
 the bilinear form is off by at most tol s_u s_v; the second tol covers the Jacobians' own rounding (a
 few eps relative, below tol >= n eps) and the sum's.
-Where a scale is zero (only the fixed pose's dofs are involved) the output must be exactly zero."""
+Where a scale is zero (only the fixed pose's dofs are involved) the output must be exactly zero.
+
+RefinedEdgeReference / check_refined add the refined criterion of marginals_ref.py to the three groups:
+the same measures against Sigma* (refined in np.longdouble; J of the projection in longdouble too), each
+group within 8 x the larger error of two plain fp64 inverses of the same H over the same entries."""
 import numpy as np
 
-from marginals_ref import Reference
+from marginals_ref import MARGIN, DenseInverses, Reference, RefinedBlocks, ratio
 
 
 def bearing_jacobians(pose, lm):
@@ -26,7 +30,7 @@ def bearing_jacobians(pose, lm):
     f = 1.0 / (gx * gx + gy * gy)
     a0, a1 = -f * gy, f * gx                             # d atan2(g) / dg
     lx, ly = lm[:, 0], lm[:, 1]
-    J = np.zeros((len(pose), 5))
+    J = np.zeros((len(pose), 5), dtype=pose.dtype)
     J[:, 3] = a0 * c - a1 * s                            # a R^T
     J[:, 4] = a0 * s + a1 * c
     J[:, 0], J[:, 1] = -J[:, 3], -J[:, 4]
@@ -38,7 +42,7 @@ def odometry_jacobians(src, dst):
     """[M, 3, 6] over [dx_s, dy_s, dth_s, dx_d, dy_d, dth_d] of the odometry prediction src -> dst."""
     c, s = np.cos(src[:, 2]), np.sin(src[:, 2])
     xd, yd = dst[:, 0], dst[:, 1]
-    J = np.zeros((len(src), 3, 6))
+    J = np.zeros((len(src), 3, 6), dtype=src.dtype)
     J[:, 0, 0], J[:, 0, 1], J[:, 0, 2] = -c, -s, -s * xd + c * yd
     J[:, 0, 3], J[:, 0, 4], J[:, 0, 5] = c, s, s * xd - c * yd
     J[:, 1, 0], J[:, 1, 1], J[:, 1, 2] = s, -c, -c * xd - s * yd
@@ -52,12 +56,16 @@ class EdgeReference(Reference):
     problem P, the lower triangle Hl of its H (reference dof numbering) and the state J is taken at
     (P's own unless given)."""
 
-    def __init__(self, P, Hl, pose_xyt=None, lm_xy=None):
-        super().__init__(P, Hl)
-        Hd = Hl.toarray()
-        H = (Hd + np.tril(Hd, -1).T)[np.ix_(self.idx, self.idx)]
+    def __init__(self, P, Hl, pose_xyt=None, lm_xy=None, dense=None):
+        super().__init__(P, Hl, dense=dense)
+        if dense is None:
+            Hd = Hl.toarray()
+            H = (Hd + np.tril(Hd, -1).T)[np.ix_(self.idx, self.idx)]
+            S = np.linalg.inv(H)
+        else:
+            S = dense.lu
         full = np.zeros((P.N, P.N))
-        full[np.ix_(self.idx, self.idx)] = np.linalg.inv(H)
+        full[np.ix_(self.idx, self.idx)] = S
         self.full = full
         sd = np.sqrt(np.diag(full))
         pose = P.pose_xyt if pose_xyt is None else pose_xyt
@@ -95,6 +103,89 @@ class EdgeReference(Reference):
     def projected_error(self, bearing_var, odom_cov):
         return max(self._scaled(bearing_var, self.bearing_var, self.bearing_var_scale),
                    self._scaled(odom_cov, self.odom_cov, self.odom_cov_scale))
+
+
+def edge_entries(P, full, pose, lm):
+    """Every edge's cross block and projected covariance out of a padded N x N matrix `full`, the
+    Jacobians evaluated in full's dtype at the state (pose, lm). Returns (entries dict, Jb, Jo, bi, oi)."""
+    three, two = np.arange(3), np.arange(2)
+    bp = 3 * P.b_pose.astype(np.int64)[:, None] + three
+    bl = 3 * P.NP + 2 * P.b_lm.astype(np.int64)[:, None] + two
+    oa = 3 * P.o_src.astype(np.int64)[:, None] + three
+    ob = 3 * P.o_dst.astype(np.int64)[:, None] + three
+    bi, oi = np.concatenate([bp, bl], axis=1), np.concatenate([oa, ob], axis=1)
+    pose, lm = pose.astype(full.dtype), lm.astype(full.dtype)
+    Jb = bearing_jacobians(pose[P.b_pose], lm[P.b_lm])
+    Jo = odometry_jacobians(pose[P.o_src], pose[P.o_dst])
+    ent = {"bearing_cross": full[bp[:, :, None], bl[:, None, :]], "odom_cross": full[oa[:, :, None], ob[:, None, :]],
+           "bearing_var": np.einsum("mi,mij,mj->m", Jb, full[bi[:, :, None], bi[:, None, :]], Jb),
+           "odom_cov": np.einsum("mui,mij,mvj->muv", Jo, full[oi[:, :, None], oi[:, None, :]], Jo)}
+    return ent, Jb, Jo, bi, oi
+
+
+class RefinedEdgeReference(EdgeReference):
+    """EdgeReference (the old bounds' Sigma_ref and tol, unchanged) plus the refined criterion of
+    marginals_ref.py for the blocks, the cross blocks and the projected covariances. Sigma* gives the
+    reference values and the scales (the Jacobians of the projection in np.longdouble); e_ref of each
+    group is the larger error of the two plain fp64 inverses (LU, Cholesky) over the same entries, their
+    projections formed in fp64. .e_ref / .e_lu / .e_chol: dicts over "blocks", "cross", "projected"."""
+
+    KEYS = {"cross": ("bearing_cross", "odom_cross"), "projected": ("bearing_var", "odom_cov")}
+
+    def __init__(self, P, Hl, pose_xyt=None, lm_xy=None):
+        d = DenseInverses(P, Hl)
+        super().__init__(P, Hl, pose_xyt, lm_xy, dense=d)
+        pose = P.pose_xyt if pose_xyt is None else pose_xyt
+        lm = P.lm_xy if lm_xy is None else lm_xy
+        self.residual = d.residual
+        star_full = d.full(d.star)
+        self.refined = RefinedBlocks(P, d, star_full)
+        sd = self.refined.sd
+        self.star, Jb, Jo, bi, oi = edge_entries(P, star_full, pose, lm)
+        three, two = slice(0, 3), slice(3, 5)
+        so = (np.abs(Jo) * sd[oi][:, None, :]).sum(axis=2)
+        self.star_scale = {"bearing_cross": sd[bi[:, three]][:, :, None] * sd[bi[:, two]][:, None, :],
+                           "odom_cross": sd[oi[:, :3]][:, :, None] * sd[oi[:, 3:]][:, None, :],
+                           "bearing_var": (np.abs(Jb) * sd[bi]).sum(axis=1) ** 2,
+                           "odom_cov": so[:, :, None] * so[:, None, :]}
+        del star_full
+        self.full = None            # the cached references keep the edges' entries only, no N x N matrix
+        self.e_lu, self.e_chol = ({"blocks": e} for e in (self.refined.e_lu, self.refined.e_chol))
+        for X, e in ((d.lu, self.e_lu), (d.chol, self.e_chol)):
+            ent = edge_entries(P, d.full(X), pose, lm)[0]
+            for group in self.KEYS:
+                errs = self.edge_errors(group, ent)
+                e[group] = float(errs.max()) if len(errs) else 0.0
+        self.e_ref = {g: max(self.e_lu[g], self.e_chol[g]) for g in self.e_lu}
+
+    def edge_errors(self, group, out):
+        """[Mb + Mo] (bearings, then odometry): per edge, the largest scaled error of its cross block
+        (group "cross") or its projected covariance ("projected") in the result dict out, against Sigma*.
+        Where the scale is zero (only the fixed pose's dofs are involved) the output must be exactly zero."""
+        each = []
+        for k in self.KEYS[group]:
+            o, ref, scale = out[k], self.star[k], self.star_scale[k]
+            zero = scale == 0.0
+            assert np.all(o[zero] == 0.0), "an entry of the fixed pose alone is not exactly zero"
+            err = np.zeros(o.shape)
+            err[~zero] = (np.abs(o - ref)[~zero] / scale[~zero]).astype(np.float64)
+            each.append(err.reshape(len(o), -1).max(axis=1) if len(o) else np.zeros(0))
+        return np.concatenate(each)
+
+
+def check_refined(ref, out, label=""):
+    """The refined criterion on one result dict: e <= MARGIN e_ref for the blocks, the cross blocks and
+    the projected covariances, each against its own e_ref. Prints e, e_ref (LU / Cholesky) and the
+    ratio of each group before asserting; returns the per-node and per-edge errors."""
+    errs = {"blocks": ref.refined.errors(out["pose_cov"], out["landmark_cov"]),
+            "cross": ref.edge_errors("cross", out), "projected": ref.edge_errors("projected", out)}
+    worst = {g: float(v.max()) if len(v) else 0.0 for g, v in errs.items()}
+    for g, e in worst.items():
+        print(f"  refined {label} {g}: e {e:.3g} e_ref {ref.e_ref[g]:.3g} (lu {ref.e_lu[g]:.3g} / chol {ref.e_chol[g]:.3g}) "
+              f"ratio {ratio(e, ref.e_ref[g]):.3g}")
+    for g, e in worst.items():
+        assert e <= MARGIN * ref.e_ref[g], (label, g, e, ref.e_ref[g], ratio(e, ref.e_ref[g]))
+    return errs
 
 
 def check_reference(ref, out, tol_cap):

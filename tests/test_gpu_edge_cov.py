@@ -8,7 +8,8 @@ import pytest
 
 import bos
 from conftest import C1, MINI
-from edge_cov_ref import EdgeReference, check_information_bound, check_reference, check_structure
+from edge_cov_ref import (EdgeReference, RefinedEdgeReference, check_information_bound, check_reference, check_refined,
+                          check_structure)
 from helpers import gpu_lower
 from marginals_ref import TOL_CAP, check_blocks, sparse_tol
 from test_edge_cov_host import edge_case_world
@@ -32,10 +33,11 @@ def _accuracy(P, S, what):
     out = S.edge_covariances()
     rows, cols, vals, _ = S.export_system()
     pose, lm = S.get_state()
-    ref = EdgeReference(P, gpu_lower(rows, cols, vals, P.N), pose, lm)
+    ref = RefinedEdgeReference(P, gpu_lower(rows, cols, vals, P.N), pose, lm)
     print(f"edge covariances gpu {what}:")
     assert out["solver_info"] == 0
     check_reference(ref, out, TOL_CAP)
+    check_refined(ref, out, what)          # within 8 x the fp64 references' own error of Sigma*
     check_blocks(P, out["pose_cov"], out["landmark_cov"])
     check_structure(P, out)
     return out, vals

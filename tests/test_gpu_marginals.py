@@ -1,7 +1,8 @@
 """Solver.marginals() (bos_marginals: J+H build, multifrontal factorization, selected inverse on the
 device) against a dense inverse of the system the same call linearised (export_system() right after
 it), against the host recursion, and for non-interference with the GN steps around it. Reference,
-error measure and the derived bound tol = n eps kappa_1(H_s): tests/marginals_ref.py."""
+error measure, the derived bound tol = n eps kappa_1(H_s) and the refined criterion (Sigma* refined in
+np.longdouble, the bound 8 e_ref measured from two fp64 inverses): tests/marginals_ref.py."""
 import types
 
 import numpy as np
@@ -10,7 +11,7 @@ import pytest
 import bos
 from conftest import C1
 from helpers import gpu_lower
-from marginals_ref import TOL_CAP, Reference, check_blocks, scaled_diff, sparse_tol
+from marginals_ref import TOL_CAP, RefinedReference, check_blocks, scaled_diff, sparse_tol
 
 pytestmark = pytest.mark.gpu
 
@@ -25,12 +26,13 @@ def c1():
 def _accuracy(P, S, what):
     pose, lm, info = S.marginals()
     rows, cols, vals, _ = S.export_system()
-    ref = Reference(P, gpu_lower(rows, cols, vals, P.N))
+    ref = RefinedReference(P, gpu_lower(rows, cols, vals, P.N))
     e = ref.error(pose, lm)
     print(f"marginals gpu {what}: n {ref.n} kappa_1 {ref.kappa:.3g} tol {ref.tol:.3g} err {e:.3g}")
     assert info == 0
     assert ref.tol <= TOL_CAP
     assert e <= ref.tol
+    ref.check_refined(pose, lm, what)      # within 8 x the fp64 references' own error of Sigma*
     check_blocks(P, pose, lm)
     return pose, lm, vals, ref
 
