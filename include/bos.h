@@ -305,6 +305,42 @@ int bos_marginals(struct bos_solver* s, double* pose_cov, double* landmark_cov, 
  * allocated: the handle stays usable and bos_marginals still works. */
 int bos_edge_covariances(struct bos_solver* s, double* bearing_cross, double* odom_cross, double* bearing_var,
                          double* odom_cov, double* pose_cov, double* landmark_cov, int32_t* solver_info);
+/* Pair covariances of the current estimate: the joint covariance of n_pairs arbitrary node pairs, whether
+ * the problem has an edge between them or not (loop-closure candidates, a bearing that may belong to a
+ * landmark the pose never observed, two landmarks that may be one). Node ids use the numbering of
+ * bos_node_owner: pose stix u is u, landmark stix l is NP + l. An id outside [0, NP + NL) gives
+ * BOS_ERR_INVALID; a mixed pair must be written (pose, landmark), the opposite order gives BOS_ERR_INVALID.
+ * Every output is [9 * n_pairs] doubles (host pointers): pair q's block row-major in the first rows * cols
+ * of its nine entries, the rest exactly 0. Any output may be NULL: it is neither computed nor downloaded.
+ * n_pairs == 0 returns BOS_OK and touches nothing.
+ *   cross      Sigma(a, b): 3 x 3, 3 x 2 or 2 x 2
+ *   projected  pose-pose: the 3 x 3 J Sigma_joint J^T of the odometry prediction a -> b; pose-landmark:
+ *              entry 0 holds the variance of the predicted bearing; landmark-landmark: the 2 x 2
+ *              covariance of l_a - l_b = S_aa + S_bb - S_ab - S_ab^T (lower triangle, mirrored)
+ *   cov_a      Sigma(a, a)
+ *   cov_b      Sigma(b, b)
+ * With H_nf = L L^T, Sigma(a, b) = (L^-1 E_a)^T (L^-1 E_b), and L^-1 E_a is non-zero only on the supernodes
+ * between a's and the root of the assembly tree: each distinct node of the call gets one sparse forward
+ * solve along its root path (one wavefront), each pair the products over the dofs its two paths share.
+ * cov_a / cov_b come from the same product (lower triangle evaluated and mirrored: bit-symmetric); they
+ * are not promised bit-equal to bos_marginals, whose summation differs. The Jacobians, the state they are
+ * evaluated at (fp64 master state, fp64 cos / sin on every handle) and the projection's arithmetic are
+ * those of bos_edge_covariances.
+ * H_nf, the damping, the kernel threshold, the state handling, the synchronous behaviour, *solver_info,
+ * the clearing of the pivot word, the "counts as a bos_linearize" rule and bos_get_last_dx afterwards are
+ * exactly those of bos_marginals.
+ * Exact rules: the fixed pose's diagonal block and every cross block that involves it are exactly zero
+ * (the projection then uses the other node's columns only); a pair (a, a) has cross == cov_a == cov_b;
+ * duplicate queries return identical bits; (b, a) returns the exact transpose of (a, b); two calls give
+ * identical bits; a query's result depends neither on the other pairs of the call nor on how the call is
+ * split into batches (a call whose path-solve buffer would pass 64 MiB runs in batches).
+ * The buffers are allocated at the first call; a handle that never calls pays nothing.
+ * BOS_ERR_SOLVER on a stalled factorization; BOS_ERR_UNSUPPORTED on BOS_SOLVER_DENSE_CHOL /
+ * BOS_SOLVER_ROCSOLVER_RF handles, on sharded handles and when a node's dofs straddle two supernodes;
+ * BOS_ERR_DEVICE (with the byte count in bos_last_error) when the feature's buffers cannot be allocated:
+ * the handle stays usable. */
+int bos_pair_covariances(struct bos_solver* s, int64_t n_pairs, const int32_t* node_a, const int32_t* node_b, double* cross,
+                         double* projected, double* cov_a, double* cov_b, int32_t* solver_info);
 /*
  * Levenberg-Marquardt with on-device step control (DESIGN.md §4 "Levenberg-Marquardt"). The objective is
  *   F(x) = sum over all edges of h(rho), rho = e^T Omega e, h(rho) = rho for rho <= kt and

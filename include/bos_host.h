@@ -115,6 +115,23 @@ int bos_plan_mf_edge_covariances(const bos_problem* problem, const bos_options* 
                                  double* bearing_cross, double* odom_cross, double* bearing_var, double* odom_cov,
                                  double* pose_cov, double* landmark_cov);
 
+/* Test hook: what bos_pair_covariances computes, in its literal host form over the host factorization of
+ * H_nf (vals as for bos_plan_mf_marginals): the same root-path walk per distinct node, the products
+ * summed in row order, and the projection by the code the device kernel runs (csrc/host/pair_cov.hpp,
+ * csrc/host/edge_cov.hpp), J evaluated at the problem's state. Ids, outputs and rules as for
+ * bos_pair_covariances; any output may be NULL. No device is used. */
+int bos_plan_mf_pair_covariances(const bos_problem* problem, const bos_options* options, const double* vals, int64_t n_pairs,
+                                 const int32_t* node_a, const int32_t* node_b, double* cross, double* projected, double* cov_a,
+                                 double* cov_b);
+
+/* The root paths of node pairs, from the plan alone (no values, no device): out[5 * n_pairs] = per pair
+ * the supernode of a, the supernode of b (-1: the fixed pose), the lowest common ancestor of the two (-1:
+ * none, the nodes hang under two roots; -2: the pair involves the fixed pose), the dofs c the two paths
+ * share (the pivots of the LCA and its ancestors; 0 without one) and the longer of the two paths, in
+ * dofs. Ids as for bos_pair_covariances. */
+int bos_plan_pair_paths(const bos_problem* problem, const bos_options* options, int64_t n_pairs, const int32_t* node_a,
+                        const int32_t* node_b, int32_t* out);
+
 /* The fronts of the plan's multifrontal tree, from the plan alone (no values, no device):
  * fronts[BOS_PLAN_FRONT_COLS * nsuper] = per supernode: k (own dofs), r (update rows), tree level
  * (leaves 0; -1 for a folded landmark, which is in no level), parent (-1 for a root), children
@@ -189,6 +206,14 @@ int bos_marginals_timing(const struct bos_solver* s, double ms[4], int64_t* sigm
  * events) and download of the outputs (host clock); *edge_bytes (may be NULL) = bytes of the feature's
  * device buffers (0 before the first call). */
 int bos_edge_covariances_timing(const struct bos_solver* s, double ms[5], int64_t* edge_bytes);
+/* Measurement helper (tools/pair_cov_time.py): the last bos_pair_covariances call's split, ms[6] = host
+ * preparation and upload (host clock), J+H build, factorization, path solve, product and projection (HIP
+ * events, summed over the call's batches) and download of the outputs (host clock); *bytes (may be NULL)
+ * = bytes of the feature's device buffers (0 before the first call). */
+int bos_pair_covariances_timing(const struct bos_solver* s, double ms[6], int64_t* bytes);
+/* Test knob: bos_pair_covariances closes a batch at max_distinct_nodes distinct nodes (at least one pair
+ * per batch) instead of at its byte budget alone; 0 restores the budget. */
+int bos_debug_set_pair_batch(struct bos_solver* s, int64_t max_distinct_nodes);
 /* Measurement helper (tools/lm_time.py): n launches of bos_cost's kernel back to back between two
  * HIP events on the handle's stream: *ms_per_pass. */
 int bos_time_cost(struct bos_solver* s, int32_t n, double* ms_per_pass);

@@ -59,6 +59,8 @@ EXPORTED_SYMBOLS = [
     "bos_lm_default_options", "bos_cost", "bos_optimize", "bos_time_cost", "bos_cpu_gn_set_kernel_threshold",
     "bos_cpu_gn_cost", "bos_cpu_gn_optimize", "bos_lm_rule_apply",
     "bos_edge_covariances", "bos_plan_mf_edge_covariances", "bos_edge_covariances_timing",
+    "bos_pair_covariances", "bos_plan_mf_pair_covariances", "bos_plan_pair_paths", "bos_pair_covariances_timing",
+    "bos_debug_set_pair_batch",
 ]
 
 # bos_lm_result.reason
@@ -213,6 +215,13 @@ def lib():
                                                          _dp, _dp, _dp, _dp]),
         "bos_edge_covariances_timing": (ctypes.c_int, [vp, _dp, ctypes.POINTER(ctypes.c_int64)]),
         "bos_marginals_timing": (ctypes.c_int, [vp, _dp, ctypes.POINTER(ctypes.c_int64)]),
+        "bos_pair_covariances": (ctypes.c_int, [vp, ctypes.c_int64, _ip, _ip, _dp, _dp, _dp, _dp, _ip]),
+        "bos_plan_mf_pair_covariances": (ctypes.c_int, [ctypes.POINTER(bos_problem), ctypes.POINTER(bos_options), _dp,
+                                                         ctypes.c_int64, _ip, _ip, _dp, _dp, _dp, _dp]),
+        "bos_plan_pair_paths": (ctypes.c_int, [ctypes.POINTER(bos_problem), ctypes.POINTER(bos_options), ctypes.c_int64,
+                                                _ip, _ip, _ip]),
+        "bos_pair_covariances_timing": (ctypes.c_int, [vp, _dp, ctypes.POINTER(ctypes.c_int64)]),
+        "bos_debug_set_pair_batch": (ctypes.c_int, [vp, ctypes.c_int64]),
         "bos_lm_default_options": (None, [ctypes.POINTER(bos_lm_options)]),
         "bos_cost": (ctypes.c_int, [vp, _dp, _dp, _ip]),
         "bos_optimize": (ctypes.c_int, [vp, ctypes.POINTER(bos_lm_options), ctypes.POINTER(bos_lm_result),
@@ -523,6 +532,59 @@ def plan_mf_edge_covariances(P: Problem, vals, solver: int = BOS_SOLVER_SCHUR, s
     _check(lib().bos_plan_mf_edge_covariances(ctypes.byref(cs), ctypes.byref(opt), _ptr(v, ctypes.c_double),
                                               *[_ptr(out[k], ctypes.c_double) for k in _EDGE_COV_ORDER]),
            "plan_mf_edge_covariances")
+    return out
+
+
+_PAIR_COV_ORDER = ("cross", "projected", "cov_a", "cov_b")
+
+
+def _pair_cov_arrays(node_a, node_b, cross: bool, projected: bool, blocks: bool):
+    """(node_a, node_b as int32 arrays, the output dict of a pair-covariance call): [n, 9] each, None
+    where not asked for."""
+    a = np.ascontiguousarray(node_a, dtype=np.int32).ravel()
+    b = np.ascontiguousarray(node_b, dtype=np.int32).ravel()
+    if len(a) != len(b):
+        raise BosError("pair covariances: node_a and node_b differ in length")
+    want = {"cross": cross, "projected": projected, "cov_a": blocks, "cov_b": blocks}
+    return a, b, {k: np.zeros((len(a), 9)) if want[k] else None for k in _PAIR_COV_ORDER}
+
+
+def pair_block(out, key: str, q: int, rows: int, cols: int) -> np.ndarray:
+    """Pair q's rows x cols block of one output of a pair-covariance call (row-major in the first
+    rows * cols of its nine entries)."""
+    return out[key][q, :rows * cols].reshape(rows, cols)
+
+
+def plan_mf_pair_covariances(P: Problem, vals, node_a, node_b, solver: int = BOS_SOLVER_SCHUR, schur_leaf: int = 0) -> dict:
+    """Host form of Solver.pair_covariances() (test hook, bos_plan_mf_pair_covariances): the root-path
+    solves and products over the host factorization of the H_nf whose stored entries are vals, projected
+    at P's state. Returns the dict of [n, 9] arrays (no solver_info)."""
+    cs = P.c_struct()
+    v = np.ascontiguousarray(vals, dtype=np.float64)
+    a, b, out = _pair_cov_arrays(node_a, node_b, True, True, True)
+    opt = options(solver, schur_leaf=schur_leaf)
+    _check(lib().bos_plan_mf_pair_covariances(ctypes.byref(cs), ctypes.byref(opt), _ptr(v, ctypes.c_double), len(a),
+                                              _ptr(a, ctypes.c_int32), _ptr(b, ctypes.c_int32),
+                                              *[_ptr(out[k], ctypes.c_double) for k in _PAIR_COV_ORDER]),
+           "plan_mf_pair_covariances")
+    return out
+
+
+# columns of plan_pair_paths
+PAIR_PATH_COLS = ("sn_a", "sn_b", "lca", "common_dofs", "longest_path_dofs")
+
+
+def plan_pair_paths(P: Problem, node_a, node_b, solver: int = BOS_SOLVER_SCHUR, schur_leaf: int = 0) -> np.ndarray:
+    """The root paths of node pairs from the plan alone (bos_plan_pair_paths): [n, 5] int32 with the
+    columns PAIR_PATH_COLS: supernode of a, supernode of b (-1: the fixed pose), their lowest common
+    ancestor (-1: none, -2: the pair involves the fixed pose), the dofs the two paths share and the
+    longer path in dofs."""
+    cs = P.c_struct()
+    a, b, _ = _pair_cov_arrays(node_a, node_b, False, False, False)
+    out = np.zeros((len(a), len(PAIR_PATH_COLS)), dtype=np.int32)
+    opt = options(solver, schur_leaf=schur_leaf)
+    _check(lib().bos_plan_pair_paths(ctypes.byref(cs), ctypes.byref(opt), len(a), _ptr(a, ctypes.c_int32),
+                                     _ptr(b, ctypes.c_int32), _ptr(out, ctypes.c_int32)), "plan_pair_paths")
     return out
 
 
@@ -933,6 +995,34 @@ class Solver:
                "bos_edge_covariances_timing")
         return {"jh_ms": ms[0], "factor_ms": ms[1], "selinv_ms": ms[2], "project_ms": ms[3], "download_ms": ms[4],
                 "edge_bytes": nb.value}
+
+    def pair_covariances(self, node_a, node_b, cross: bool = True, projected: bool = True, blocks: bool = True) -> dict:
+        """Joint covariances of arbitrary node pairs at the current estimate (bos_pair_covariances). Node
+        ids: pose stix u is u, landmark stix l is NP + l; a mixed pair is (pose, landmark). Returns a dict
+        of [n, 9] arrays, pair q's block row-major in the first rows * cols entries of row q (pair_block):
+        cross, projected, cov_a and cov_b (blocks), and solver_info; outputs not asked for are None."""
+        a, b, out = _pair_cov_arrays(node_a, node_b, cross, projected, blocks)
+        info = ctypes.c_int32(0)
+        _check(lib().bos_pair_covariances(self._h, len(a), _ptr(a, ctypes.c_int32), _ptr(b, ctypes.c_int32),
+                                          *[_ptr(out[k], ctypes.c_double) for k in _PAIR_COV_ORDER], ctypes.byref(info)),
+               "bos_pair_covariances")
+        out["solver_info"] = info.value
+        return out
+
+    def pair_covariances_timing(self) -> dict:
+        """The last pair_covariances() call's split in ms and the feature's device bytes
+        (bos_pair_covariances_timing)."""
+        ms = np.zeros(6)
+        nb = ctypes.c_int64(0)
+        _check(lib().bos_pair_covariances_timing(self._h, _ptr(ms, ctypes.c_double), ctypes.byref(nb)),
+               "bos_pair_covariances_timing")
+        return {"prepare_ms": ms[0], "jh_ms": ms[1], "factor_ms": ms[2], "path_ms": ms[3], "product_ms": ms[4],
+                "download_ms": ms[5], "pair_bytes": nb.value}
+
+    def debug_set_pair_batch(self, max_distinct_nodes: int):
+        """Test knob (bos_debug_set_pair_batch): pair_covariances() closes a batch at this many distinct
+        nodes; 0 restores the byte budget."""
+        _check(lib().bos_debug_set_pair_batch(self._h, max_distinct_nodes), "bos_debug_set_pair_batch")
 
     def cost(self) -> dict:
         """The objective F at the current state, the plain chi2 and the count of edges beyond the

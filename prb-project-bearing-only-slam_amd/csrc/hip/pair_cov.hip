@@ -1,0 +1,371 @@
+// Pair covariances: Sigma_ab = (L^-1 E_a)^T (L^-1 E_b) from the finished L panels of hip/multifrontal.hip
+// (host/pair_cov.hpp). All arithmetic is fp64; every wave works alone: no flags, waits, tickets or atomics.
+//
+// pair_path_kernel: one wavefront (one workgroup) per distinct node, d = 3 or 2 right-hand sides, walking
+// from the node's supernode to the root. Between fronts w (m rows x d) lives in one of two LDS buffers:
+// the front's update rows are scattered through rmap into the other, zeroed, buffer, which becomes the
+// parent's w. Two front classes:
+//   m <= 64: one row per lane in registers, the pivot's y broadcast by v_readlane. The panel's addresses
+//            do not depend on w, so eight columns are loaded (coalesced, lane = row) before the eight
+//            dependent pivot steps that use them; the lane on the diagonal holds L(j, j) in the same load.
+//   m > 64:  w stays in LDS, rows strided over the lanes. Four columns are loaded for a block of up to
+//            384 rows, then the four pivots are applied; the first row block holds the pivot rows
+//            themselves and fixes the four y (kept in registers for the remaining row blocks).
+// Every row sees its pivots in ascending order in both classes, as the host twin's loop does.
+// pair_product_kernel: one wavefront per block; a lane sums its rows t = lane, lane + 64, ... in order,
+// then the wave reduces by xor-butterfly (a fixed order). Diagonal blocks are the pair (a, a) over the
+// whole path, lower triangle evaluated and mirrored.
+// pair_project_kernel: one thread per query (host/pair_cov.hpp pair_cov_query).
+#include "pair_cov.hpp"
+
+#include <algorithm>
+
+namespace bos {
+namespace dev {
+
+namespace {
+
+constexpr int kWave = 64;
+constexpr int kRegCols = 8;              // m <= 64: panel columns loaded ahead of their pivots
+constexpr int kLdsCols = 4, kLdsSlots = 6;   // m > 64: columns per chunk, rows per lane and row block
+constexpr int kProdBlock = 256, kProjBlock = 256;
+
+struct PathArgs {
+    const int32_t *k, *r, *parent, *rmap;
+    const int64_t *L_off, *rmap_off;
+    const double* L;
+    const int32_t *n_sn, *n_loc, *n_d;
+    const int64_t* y_off;
+    double* Y;
+    int buf;   // doubles of one w buffer
+};
+
+__device__ __forceinline__ double readlane_d(double x, int l) {
+    const long long b = __double_as_longlong(x);
+    const int lo = __builtin_amdgcn_readlane((int)(b & 0xffffffffll), l);
+    const int hi = __builtin_amdgcn_readlane((int)(b >> 32), l);
+    return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
+}
+
+template <int D> __device__ void path_solve(const PathArgs& a, int node, double* wl, double* wn) {
+    const int lane = threadIdx.x;
+    int s = a.n_sn[node], j0 = a.n_loc[node];
+    double* Y = a.Y + a.y_off[node];
+    {   // the unit columns at the node's dofs
+        const int m = a.k[s] + a.r[s];
+        for (int idx = lane; idx < m * D; idx += kWave) wl[idx] = 0.0;
+        __syncthreads();
+        if (lane < D) wl[(j0 + lane) * D + lane] = 1.0;
+        __syncthreads();
+    }
+    int64_t base = 0;
+    for (;;) {
+        const int k = a.k[s], r = a.r[s], m = k + r;
+        const double* Ls = a.L + a.L_off[s];
+        const int p = r > 0 ? a.parent[s] : -1;
+        const int mp = p >= 0 ? a.k[p] + a.r[p] : 0;
+        const int32_t* rm = a.rmap + a.rmap_off[s];
+        if (m <= kWave) {
+            double w[D];
+#pragma unroll
+            for (int c = 0; c < D; ++c) w[c] = lane < m ? wl[lane * D + c] : 0.0;
+            for (int jb = j0; jb < k; jb += kRegCols) {
+                double col[kRegCols];
+#pragma unroll
+                for (int u = 0; u < kRegCols; ++u) {
+                    const int j = jb + u;
+                    col[u] = j < k && lane >= j && lane < m ? Ls[lane + (int64_t)j * m] : 0.0;
+                }
+#pragma unroll
+                for (int u = 0; u < kRegCols; ++u) {
+                    const int j = jb + u;
+                    if (j < k) {
+                        const double dg = readlane_d(col[u], j);
+#pragma unroll
+                        for (int c = 0; c < D; ++c) {
+                            const double y = readlane_d(w[c], j) / dg;
+                            w[c] = lane == j ? y : (lane > j ? w[c] - col[u] * y : w[c]);
+                        }
+                    }
+                }
+            }
+            if (lane < k) {
+#pragma unroll
+                for (int c = 0; c < D; ++c) Y[(base + lane) * D + c] = w[c];
+            }
+            if (p < 0) break;
+            for (int idx = lane; idx < mp * D; idx += kWave) wn[idx] = 0.0;
+            __syncthreads();
+            if (lane >= k && lane < m) {
+                const int dst = rm[lane - k];
+#pragma unroll
+                for (int c = 0; c < D; ++c) wn[dst * D + c] = w[c];
+            }
+        } else {
+            for (int jb = j0; jb < k; jb += kLdsCols) {
+                double y[kLdsCols][D];
+                for (int rb = jb; rb < m; rb += kWave * kLdsSlots) {
+                    const bool first = rb == jb;   // the row block that holds the chunk's pivot rows
+                    double col[kLdsCols][kLdsSlots];
+#pragma unroll
+                    for (int u = 0; u < kLdsCols; ++u)
+#pragma unroll
+                        for (int sl = 0; sl < kLdsSlots; ++sl) {
+                            const int j = jb + u, i = rb + lane + kWave * sl;
+                            col[u][sl] = j < k && i < m && i >= j ? Ls[i + (int64_t)j * m] : 0.0;
+                        }
+#pragma unroll
+                    for (int u = 0; u < kLdsCols; ++u) {
+                        const int j = jb + u;
+                        if (j < k) {
+                            if (first) {
+                                const double dg = readlane_d(col[u][0], u);   // lane u, slot 0: row jb + u = j
+#pragma unroll
+                                for (int c = 0; c < D; ++c) y[u][c] = wl[j * D + c] / dg;
+                            }
+#pragma unroll
+                            for (int sl = 0; sl < kLdsSlots; ++sl) {
+                                const int i = rb + lane + kWave * sl;
+                                if (i < m && i >= j) {
+#pragma unroll
+                                    for (int c = 0; c < D; ++c) wl[i * D + c] = i == j ? y[u][c] : wl[i * D + c] - col[u][sl] * y[u][c];
+                                }
+                            }
+                            if (first) __syncthreads();   // the next pivot's row is in this block
+                        }
+                    }
+                }
+                __syncthreads();   // the next chunk deals the rows to other lanes
+            }
+            for (int idx = lane; idx < k * D; idx += kWave) Y[base * D + idx] = wl[idx];
+            if (p < 0) break;
+            for (int idx = lane; idx < mp * D; idx += kWave) wn[idx] = 0.0;
+            __syncthreads();
+            for (int t = lane; t < r; t += kWave) {
+                const int dst = rm[t];
+#pragma unroll
+                for (int c = 0; c < D; ++c) wn[dst * D + c] = wl[(k + t) * D + c];
+            }
+        }
+        __syncthreads();
+        double* sw = wl;
+        wl = wn;
+        wn = sw;
+        base += k;
+        s = p;
+        j0 = 0;
+    }
+}
+
+// one wavefront per workgroup: the barriers above are the wave's own (trip counts differ between nodes)
+__global__ __launch_bounds__(kWave) void pair_path_kernel(const PathArgs a) {
+    extern __shared__ double pair_lds[];
+    const int node = blockIdx.x;
+    if (a.n_d[node] == 3) path_solve<3>(a, node, pair_lds, pair_lds + a.buf);
+    else path_solve<2>(a, node, pair_lds, pair_lds + a.buf);
+}
+
+struct ProdArgs {
+    int n_diag, NP;          // diagonal-block tasks (one per distinct node, or 0), then the queries' cross blocks
+    int64_t n_cross;
+    const int64_t* y_off;
+    const int32_t *n_d, *n_len;
+    const int32_t *q_a, *q_b, *q_slot_a, *q_slot_b, *q_off_a, *q_off_b, *q_c;
+    const double* Y;
+    double *diag, *cross;
+};
+
+__global__ __launch_bounds__(kProdBlock) void pair_product_kernel(const ProdArgs a) {
+    const int64_t task = (int64_t)blockIdx.x * (kProdBlock / kWave) + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (task >= a.n_diag + a.n_cross) return;
+    const double *Ya, *Yb;
+    double* dst;
+    int da, db, c;
+    int64_t oa, ob;
+    const bool lower = task < a.n_diag;
+    if (lower) {
+        Ya = Yb = a.Y + a.y_off[task];
+        da = db = a.n_d[task];
+        c = a.n_len[task];
+        oa = ob = 0;
+        dst = a.diag + 9 * task;
+    } else {
+        const int64_t q = task - a.n_diag;
+        const int sa = a.q_slot_a[q], sb = a.q_slot_b[q];
+        da = a.q_a[q] < a.NP ? 3 : 2;
+        db = a.q_b[q] < a.NP ? 3 : 2;
+        c = sa >= 0 && sb >= 0 ? a.q_c[q] : 0;
+        Ya = a.Y + (c > 0 ? a.y_off[sa] : 0);
+        Yb = a.Y + (c > 0 ? a.y_off[sb] : 0);
+        oa = a.q_off_a[q];
+        ob = a.q_off_b[q];
+        dst = a.cross + 9 * q;
+    }
+    double acc[3][3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) acc[i][j] = 0.0;
+    for (int t = lane; t < c; t += kWave) {
+        double ya[3], yb[3];
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            ya[i] = i < da ? Ya[(oa + t) * da + i] : 0.0;
+            yb[i] = i < db ? Yb[(ob + t) * db + i] : 0.0;
+        }
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+#pragma unroll
+            for (int j = 0; j < 3; ++j)
+                if (!lower || j <= i) acc[i][j] = fma(ya[i], yb[j], acc[i][j]);
+    }
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j)
+            for (int o = 32; o > 0; o >>= 1) acc[i][j] += __shfl_xor(acc[i][j], o);
+    if (lane == 0) {
+        double out[9];
+#pragma unroll
+        for (int e = 0; e < 9; ++e) out[e] = 0.0;
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+#pragma unroll
+            for (int j = 0; j < 3; ++j)
+                if (i < da && j < db) out[i * db + j] = lower && j > i ? acc[j][i] : acc[i][j];
+#pragma unroll
+        for (int e = 0; e < 9; ++e) dst[e] = out[e];
+    }
+}
+
+__global__ __launch_bounds__(kProjBlock) void pair_project_kernel(const PairQueryIn in, const PairQueryOut out, int64_t n) {
+    const int64_t q = (int64_t)blockIdx.x * kProjBlock + threadIdx.x;
+    if (q < n) pair_cov_query(in, out, q);
+}
+
+}  // namespace
+
+struct PairCov {
+    char* arena = nullptr;
+    int64_t bytes = 0;
+    // the uploaded batch
+    int32_t n_nodes = 0;
+    int64_t n_queries = 0;
+    bool want[4] = {false, false, false, false};
+    int64_t* y_off = nullptr;
+    int32_t *n_sn = nullptr, *n_loc = nullptr, *n_d = nullptr, *n_len = nullptr;
+    int32_t *q_a = nullptr, *q_b = nullptr, *q_slot_a = nullptr, *q_slot_b = nullptr, *q_off_a = nullptr, *q_off_b = nullptr, *q_c = nullptr;
+    double *Y = nullptr, *diag = nullptr, *cross = nullptr, *out[4] = {};
+};
+
+PairCov* pair_cov_create() { return new PairCov(); }
+
+void pair_cov_destroy(PairCov* p) {
+    if (!p) return;
+    if (p->arena) (void)hipFree(p->arena);
+    delete p;
+}
+
+int64_t pair_cov_bytes(const PairCov* p) { return p ? p->bytes : 0; }
+
+int pair_cov_upload(PairCov* p, const PairCovBatch& b, const bool want[4], std::string& err) {
+    // one arena: [index arrays | Y | diagonal blocks | cross blocks | outputs], every part aligned to 256 bytes
+    int64_t bytes = 0;
+    auto take = [&](int64_t count, int64_t elem) {
+        const int64_t off = bytes;
+        bytes += (std::max<int64_t>(count, 1) * elem + 255) / 256 * 256;
+        return off;
+    };
+    const int64_t nn = b.n_nodes, nq = b.n_queries;
+    const bool need_diag = want[1] || want[2] || want[3], need_cross = want[0] || want[1];
+    const int64_t o_yoff = take(nn, 8), o_nsn = take(nn, 4), o_nloc = take(nn, 4), o_nd = take(nn, 4), o_nlen = take(nn, 4);
+    int64_t o_q[7];
+    for (int i = 0; i < 7; ++i) o_q[i] = take(nq, 4);
+    const int64_t o_Y = take(b.y_count, 8), o_diag = take(need_diag ? 9 * nn : 0, 8), o_cross = take(need_cross ? 9 * nq : 0, 8);
+    int64_t o_out[4];
+    for (int i = 0; i < 4; ++i) o_out[i] = take(want[i] ? 9 * nq : 0, 8);
+    if (bytes > p->bytes) {
+        if (p->arena) (void)hipFree(p->arena);
+        p->arena = nullptr;
+        p->bytes = 0;
+        if (hipMalloc((void**)&p->arena, (size_t)bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            p->arena = nullptr;
+            err = "bos_pair_covariances: device allocation of " + std::to_string(bytes) + " bytes failed";
+            return -2;
+        }
+        p->bytes = bytes;
+    }
+    char* A = p->arena;
+    auto up = [&](int64_t off, const void* src, int64_t count, int64_t elem) {
+        return count == 0 || hipMemcpy(A + off, src, (size_t)(count * elem), hipMemcpyHostToDevice) == hipSuccess;
+    };
+    const int32_t* qs[7] = {b.q_a, b.q_b, b.q_slot_a, b.q_slot_b, b.q_off_a, b.q_off_b, b.q_c};
+    bool ok = up(o_yoff, b.y_off, nn, 8) && up(o_nsn, b.n_sn, nn, 4) && up(o_nloc, b.n_loc, nn, 4) && up(o_nd, b.n_d, nn, 4) &&
+              up(o_nlen, b.n_len, nn, 4);
+    for (int i = 0; i < 7 && ok; ++i) ok = up(o_q[i], qs[i], nq, 4);
+    if (!ok) {
+        (void)hipGetLastError();
+        err = "bos_pair_covariances: upload of the batch failed";
+        return -2;
+    }
+    p->n_nodes = b.n_nodes;
+    p->n_queries = nq;
+    for (int i = 0; i < 4; ++i) p->want[i] = want[i];
+    p->y_off = (int64_t*)(A + o_yoff);
+    p->n_sn = (int32_t*)(A + o_nsn); p->n_loc = (int32_t*)(A + o_nloc); p->n_d = (int32_t*)(A + o_nd); p->n_len = (int32_t*)(A + o_nlen);
+    p->q_a = (int32_t*)(A + o_q[0]); p->q_b = (int32_t*)(A + o_q[1]); p->q_slot_a = (int32_t*)(A + o_q[2]);
+    p->q_slot_b = (int32_t*)(A + o_q[3]); p->q_off_a = (int32_t*)(A + o_q[4]); p->q_off_b = (int32_t*)(A + o_q[5]);
+    p->q_c = (int32_t*)(A + o_q[6]);
+    p->Y = (double*)(A + o_Y);
+    p->diag = need_diag ? (double*)(A + o_diag) : nullptr;
+    p->cross = need_cross ? (double*)(A + o_cross) : nullptr;
+    for (int i = 0; i < 4; ++i) p->out[i] = want[i] ? (double*)(A + o_out[i]) : nullptr;
+    return 0;
+}
+
+int pair_cov_enqueue(PairCov* p, const MfView& v, int max_m, int NP, const double* pose, const double* lm, hipStream_t s,
+                     hipEvent_t after_solve, PairCovOut* out, std::string& err) {
+    if (!p->arena) { err = "bos_pair_covariances: no batch uploaded"; return -1; }
+    if (max_m > kPairMaxM) { err = "bos_pair_covariances: a front of " + std::to_string(max_m) + " rows exceeds the path solve's LDS"; return -1; }
+    hipError_t e = hipSuccess;
+    if (p->n_nodes > 0) {
+        PathArgs a;
+        a.k = v.k; a.r = v.r; a.parent = v.parent; a.rmap = v.rmap; a.L_off = v.L_off; a.rmap_off = v.rmap_off; a.L = v.L;
+        a.n_sn = p->n_sn; a.n_loc = p->n_loc; a.n_d = p->n_d; a.y_off = p->y_off; a.Y = p->Y;
+        a.buf = max_m * 3;
+        pair_path_kernel<<<p->n_nodes, kWave, 2 * (size_t)a.buf * sizeof(double), s>>>(a);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess && after_solve) e = hipEventRecord(after_solve, s);
+    ProdArgs g;
+    g.n_diag = p->diag ? p->n_nodes : 0;
+    g.n_cross = p->cross ? p->n_queries : 0;
+    g.NP = NP;
+    g.y_off = p->y_off; g.n_d = p->n_d; g.n_len = p->n_len;
+    g.q_a = p->q_a; g.q_b = p->q_b; g.q_slot_a = p->q_slot_a; g.q_slot_b = p->q_slot_b; g.q_off_a = p->q_off_a; g.q_off_b = p->q_off_b;
+    g.q_c = p->q_c;
+    g.Y = p->Y; g.diag = p->diag; g.cross = p->cross;
+    const int64_t tasks = g.n_diag + g.n_cross, per = kProdBlock / kWave;
+    if (e == hipSuccess && tasks > 0) {
+        pair_product_kernel<<<(unsigned)((tasks + per - 1) / per), kProdBlock, 0, s>>>(g);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess && p->n_queries > 0) {
+        PairQueryIn in;
+        in.NP = NP; in.pose = pose; in.lm = lm;
+        in.node_a = p->q_a; in.node_b = p->q_b; in.slot_a = p->q_slot_a; in.slot_b = p->q_slot_b;
+        in.crossbuf = p->cross; in.diag = p->diag;
+        PairQueryOut o;
+        o.cross = p->out[0]; o.projected = p->out[1]; o.cov_a = p->out[2]; o.cov_b = p->out[3];
+        pair_project_kernel<<<(unsigned)((p->n_queries + kProjBlock - 1) / kProjBlock), kProjBlock, 0, s>>>(in, o, p->n_queries);
+        e = hipGetLastError();
+    }
+    if (e != hipSuccess) { err = std::string("bos_pair_covariances: launch: ") + hipGetErrorString(e); return -2; }
+    out->cross = p->out[0]; out->projected = p->out[1]; out->cov_a = p->out[2]; out->cov_b = p->out[3];
+    return 0;
+}
+
+}  // namespace dev
+}  // namespace bos

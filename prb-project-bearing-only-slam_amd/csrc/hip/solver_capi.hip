@@ -35,6 +35,7 @@
 #include "kernels.hpp"
 #include "lm.hpp"
 #include "multifrontal.hpp"
+#include "pair_cov.hpp"
 #include "selinv.hpp"
 
 namespace {
@@ -205,6 +206,14 @@ struct bos_solver {
     double marg_ms[4] = {};
     // the last bos_edge_covariances: the same, the projection kernel (events) before the download
     double edge_ms[5] = {};
+    // bos_pair_covariances (hip/pair_cov.hpp): the static path data and the device arena, both built at
+    // the first call; the last call's split (host preparation and upload, J+H, factorization, path solve,
+    // product and projection, download); bos_debug_set_pair_batch's limit (0: the byte budget alone)
+    bos::PairPaths pair_paths;
+    bool pair_paths_built = false;
+    bos::dev::PairCov* pair = nullptr;
+    double pair_ms[6] = {};
+    int64_t pair_batch_nodes = 0;
     // ---- bos_cost / bos_optimize (hip/lm.hpp). The fp64 originals of what the cost pass reads and the
     // J+H keeps only in T: odometry z / information (upper triangle) and the bearing weights (has_w)
     std::vector<double> h_oz, h_oom, h_bw;
@@ -1339,6 +1348,7 @@ int bos_destroy(bos_solver* s) {
     for (void* m : s->peer_maps) (void)hipIpcCloseMemHandle(m);
     if (s->rf) rocsolver_destroy_rfinfo(s->rf);
     if (s->mf) bos::dev::mf_destroy(s->mf);
+    bos::dev::pair_cov_destroy(s->pair);
     if (s->rb) rocblas_destroy_handle(s->rb);
     if (s->comm) ncclCommDestroy(s->comm);
     for (hipEvent_t& e : s->ev)
@@ -2327,6 +2337,109 @@ int bos_marginals_timing(const bos_solver* s, double ms[4], int64_t* sigma_bytes
     if (!s || !ms) return fail(BOS_ERR_INVALID, "null argument");
     for (int i = 0; i < 4; ++i) ms[i] = s->marg_ms[i];
     if (sigma_bytes) *sigma_bytes = s->mf ? bos::dev::mf_selinv_sigma_bytes(s->mf) : 0;
+    return BOS_OK;
+}
+
+int bos_pair_covariances(bos_solver* s, int64_t n_pairs, const int32_t* node_a, const int32_t* node_b, double* cross,
+                         double* projected, double* cov_a, double* cov_b, int32_t* solver_info) {
+    const char* name = "bos_pair_covariances";
+    if (!s) return fail(BOS_ERR_INVALID, "null handle");
+    if (!uses_mf(s))
+        return fail(BOS_ERR_UNSUPPORTED, std::string(name) + " needs a multifrontal solver (BOS_SOLVER_SCHUR or BOS_SOLVER_SUPERNODAL)");
+    if (s->sharded || s->obs || s->world > 1 || s->comm || s->external || s->p2p)
+        return fail(BOS_ERR_UNSUPPORTED, std::string(name) + " on a sharded handle (a rank holds part of the factor)");
+    if (n_pairs < 0 || (n_pairs > 0 && (!node_a || !node_b))) return fail(BOS_ERR_INVALID, std::string(name) + ": bad argument");
+    if (n_pairs == 0) return BOS_OK;
+    if (!bos::pair_ids_valid(s->NP, s->NL, n_pairs, node_a, node_b))
+        return fail(BOS_ERR_INVALID, std::string(name) + ": a node id outside [0, NP + NL), or a mixed pair not written (pose, landmark)");
+    double* const outs[4] = {cross, projected, cov_a, cov_b};
+    bool want[4];
+    for (int i = 0; i < 4; ++i) want[i] = outs[i] != nullptr;
+    HIP_TRY(hipSetDevice(s->device));
+    if (solver_info) *solver_info = 0;
+    for (double& m : s->pair_ms) m = 0.0;
+    if (s->plan.n == 0) {   // the fixed pose alone
+        for (int i = 0; i < 4; ++i)
+            if (want[i]) std::fill(outs[i], outs[i] + 9 * n_pairs, 0.0);
+        return BOS_OK;
+    }
+    typedef std::chrono::steady_clock Clock;
+    auto ms_since = [](Clock::time_point t0) { return std::chrono::duration<double, std::milli>(Clock::now() - t0).count(); };
+    auto t_prep = Clock::now();
+    if (!s->pair_paths_built) {
+        std::string err;
+        if (!bos::pair_paths_build(s->plan, s->pair_paths, err)) return fail(BOS_ERR_UNSUPPORTED, err);
+        if (s->pair_paths.max_m > bos::dev::kPairMaxM)
+            return fail(BOS_ERR_UNSUPPORTED, std::string(name) + ": a front exceeds the path solve's LDS");
+        s->pair_paths_built = true;
+    }
+    if (!s->pair) s->pair = bos::dev::pair_cov_create();
+    s->pair_ms[0] += ms_since(t_prep);
+    // the system of bos_linearize and its factorization, as bos_marginals enqueues them (bos_step returns
+    // on its status word, before the stream has drained: everything below is ordered after it by the stream)
+    int rc;
+    HIP_TRY(hipEventRecord(s->ev[0], s->stream));
+    if ((rc = enqueue_linearize(s))) return rc;
+    HIP_TRY(hipEventRecord(s->ev[1], s->stream));
+    if ((rc = enqueue_solver_inputs(s))) return rc;   // opens the flows' epoch, as a step does
+    HIP_TRY(bos::dev::mf_factor(s->mf, 0, mf_matrix(s), s->d_rhs, s->stream));
+    s->have_dx = false;   // d_rhs now holds L^-1 b of this factorization
+    HIP_TRY(hipEventRecord(s->ev[2], s->stream));
+    // the factorization's word, read and cleared before anything reads the panels: a step expects it zero
+    int32_t info = 0;
+    HIP_TRY(hipMemcpyAsync(&info, bos::dev::mf_info_ptr(s->mf), sizeof(info), hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipMemsetAsync(bos::dev::mf_info_ptr(s->mf), 0, sizeof(int32_t), s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    s->pair_ms[1] = elapsed(s->ev[0], s->ev[1]);
+    s->pair_ms[2] = elapsed(s->ev[1], s->ev[2]);
+    if (info & bos::dev::kMfStall)
+        return fail(BOS_ERR_SOLVER, "sparse factorization aborted: a dataflow dependency wait timed out");
+    const bos::dev::MfView view = bos::dev::mf_view(s->mf);
+    const int64_t max_nodes = s->pair_batch_nodes > 0 ? std::max<int64_t>(s->pair_batch_nodes, 2) : INT32_MAX;
+    std::vector<int32_t> slot_of((size_t)s->NP + s->NL, -1);
+    bos::PairBatchHost B;
+    for (int64_t q0 = 0; q0 < n_pairs; q0 += B.nq) {
+        t_prep = Clock::now();
+        bos::pair_batch_build(s->plan, s->pair_paths, n_pairs, node_a, node_b, q0, max_nodes,
+                              bos::dev::kPairYBudgetBytes / (int64_t)sizeof(double), bos::dev::kPairMaxQueries, slot_of, B);
+        bos::dev::PairCovBatch b;
+        b.n_nodes = (int32_t)B.n_node.size(); b.n_queries = B.nq; b.y_count = B.y_count;
+        b.y_off = B.y_off.data(); b.n_sn = B.n_sn.data(); b.n_loc = B.n_loc.data(); b.n_d = B.n_d.data(); b.n_len = B.n_len.data();
+        b.q_a = node_a + q0; b.q_b = node_b + q0; b.q_slot_a = B.q_slot_a.data(); b.q_slot_b = B.q_slot_b.data();
+        b.q_off_a = B.q_off_a.data(); b.q_off_b = B.q_off_b.data(); b.q_c = B.q_c.data();
+        std::string err;
+        int prc = bos::dev::pair_cov_upload(s->pair, b, want, err);
+        if (prc) return fail(prc == -1 ? BOS_ERR_UNSUPPORTED : BOS_ERR_DEVICE, err);
+        s->pair_ms[0] += ms_since(t_prep);
+        bos::dev::PairCovOut res;
+        HIP_TRY(hipEventRecord(s->ev[3], s->stream));
+        prc = bos::dev::pair_cov_enqueue(s->pair, view, s->pair_paths.max_m, s->NP, s->d_pose, s->d_lm, s->stream, s->ev[4], &res, err);
+        hipError_t e = hipEventRecord(s->ev[5], s->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
+        HIP_TRY(e);
+        if (prc) return fail(prc == -1 ? BOS_ERR_UNSUPPORTED : BOS_ERR_DEVICE, err);
+        s->pair_ms[3] += elapsed(s->ev[3], s->ev[4]);
+        s->pair_ms[4] += elapsed(s->ev[4], s->ev[5]);
+        const auto t_dl = Clock::now();
+        const double* dev[4] = {res.cross, res.projected, res.cov_a, res.cov_b};
+        for (int i = 0; i < 4; ++i)
+            if (want[i]) HIP_TRY(hipMemcpy(outs[i] + 9 * q0, dev[i], 9 * (size_t)B.nq * sizeof(double), hipMemcpyDeviceToHost));
+        s->pair_ms[5] += ms_since(t_dl);
+    }
+    if (solver_info) *solver_info = info;
+    return BOS_OK;
+}
+
+int bos_pair_covariances_timing(const bos_solver* s, double ms[6], int64_t* bytes) {
+    if (!s || !ms) return fail(BOS_ERR_INVALID, "null argument");
+    for (int i = 0; i < 6; ++i) ms[i] = s->pair_ms[i];
+    if (bytes) *bytes = bos::dev::pair_cov_bytes(s->pair);
+    return BOS_OK;
+}
+
+int bos_debug_set_pair_batch(bos_solver* s, int64_t max_distinct_nodes) {
+    if (!s || max_distinct_nodes < 0) return fail(BOS_ERR_INVALID, "bad argument");
+    s->pair_batch_nodes = max_distinct_nodes;
     return BOS_OK;
 }
 

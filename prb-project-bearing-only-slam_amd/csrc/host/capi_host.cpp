@@ -11,6 +11,7 @@
 
 #include "../../../include/bos_host.h"
 #include "edge_cov.hpp"
+#include "pair_cov.hpp"
 #include "g2o_utils.hpp"
 #include "host_mf.hpp"
 #include "plan.hpp"
@@ -497,6 +498,94 @@ int bos_plan_mf_edge_covariances(const bos_problem* pb, const bos_options* optio
     for (int64_t e = 0; e < pi.Mo; ++e) bos::edge_cov_odometry(in, o, e);
     if (pose_cov) std::copy(pc.begin(), pc.end() - 1, pose_cov);
     if (landmark_cov) std::copy(lc.begin(), lc.end() - 1, landmark_cov);
+    return BOS_OK;
+}
+
+namespace {
+// the one-GPU multifrontal plan of the pair hooks and its path data
+static int pair_plan(const bos_problem* pb, const bos_options* options, bos::ProblemIndex& pi, bos::Plan& P, bos::PairPaths& pp) {
+    bos_options opt;
+    int fmode = 0;
+    int rc = plan_args(pb, options, pi, fmode, opt);
+    if (rc) return rc;
+    if (opt.solver != BOS_SOLVER_SUPERNODAL && opt.solver != BOS_SOLVER_SCHUR)
+        return hfail(BOS_ERR_INVALID, "pair covariances need a multifrontal solver");
+    std::string err;
+    rc = bos::build_plan(pi, 0, 1, fmode, P, err);
+    if (rc) return hfail(rc, err);
+    if (!bos::pair_paths_build(P, pp, err)) return hfail(BOS_ERR_UNSUPPORTED, err);
+    return BOS_OK;
+}
+}  // namespace
+
+// Test hook: bos_pair_covariances in its literal host form (csrc/host/pair_cov.hpp): the host
+// factorization, one root-path solve per distinct node, the products in row order and the per-query
+// projection the device kernel runs, at the problem's state (theta wrapped as bos_create wraps it).
+int bos_plan_mf_pair_covariances(const bos_problem* pb, const bos_options* options, const double* vals, int64_t n_pairs,
+                                 const int32_t* node_a, const int32_t* node_b, double* cross, double* projected, double* cov_a,
+                                 double* cov_b) {
+    if (!pb || !vals || !pb->pose_xyt || (!pb->landmark_xy && pb->num_landmarks > 0) || n_pairs < 0 ||
+        (n_pairs > 0 && (!node_a || !node_b)))
+        return hfail(BOS_ERR_INVALID, "bad argument");
+    if (n_pairs == 0) return BOS_OK;
+    if (!bos::pair_ids_valid(pb->num_poses, pb->num_landmarks, n_pairs, node_a, node_b))
+        return hfail(BOS_ERR_INVALID, "bos_pair_covariances: a node id outside [0, NP + NL), or a mixed pair not written (pose, landmark)");
+    bos::ProblemIndex pi;
+    bos::Plan P;
+    bos::PairPaths pp;
+    const int rc = pair_plan(pb, options, pi, P, pp);
+    if (rc) return rc;
+    const std::vector<double> rhs(P.n, 0.0);
+    bos::HostMf M(P, vals, rhs.data());
+    M.factor([](int) { return true; });
+    std::vector<int32_t> slot_of((size_t)P.NP + P.NL, -1);
+    bos::PairBatchHost B;
+    bos::pair_batch_build(P, pp, n_pairs, node_a, node_b, 0, INT64_MAX, INT64_MAX, INT64_MAX, slot_of, B);
+    const size_t nn = B.n_node.size();
+    std::vector<double> Y((size_t)B.y_count + 1), diag(9 * nn + 1), cb(9 * (size_t)n_pairs);
+    for (size_t i = 0; i < nn; ++i) {
+        double* Yi = Y.data() + B.y_off[i];
+        bos::pair_path_solve_host(P.mf, pp, M.L.data(), B.n_sn[i], B.n_loc[i], B.n_d[i], Yi);
+        bos::pair_product_host(Yi, 0, B.n_d[i], Yi, 0, B.n_d[i], B.n_len[i], true, diag.data() + 9 * i);
+    }
+    for (int64_t q = 0; q < n_pairs; ++q) {
+        const int sa = B.q_slot_a[q], sb = B.q_slot_b[q];
+        const int da = node_a[q] < P.NP ? 3 : 2, db = node_b[q] < P.NP ? 3 : 2;
+        const bool free2 = sa >= 0 && sb >= 0;
+        bos::pair_product_host(Y.data() + (free2 ? B.y_off[sa] : 0), B.q_off_a[q], da, Y.data() + (free2 ? B.y_off[sb] : 0), B.q_off_b[q],
+                               db, free2 ? B.q_c[q] : 0, false, cb.data() + 9 * q);
+    }
+    std::vector<double> pose(pb->pose_xyt, pb->pose_xyt + 3 * (size_t)P.NP);
+    for (int i = 0; i < P.NP; ++i) pose[3 * i + 2] = bos::normalized_angle<double>(bos::smallest_angle<double>(pose[3 * i + 2]));
+    bos::PairQueryIn in;
+    in.NP = P.NP; in.pose = pose.data(); in.lm = pb->landmark_xy;
+    in.node_a = node_a; in.node_b = node_b; in.slot_a = B.q_slot_a.data(); in.slot_b = B.q_slot_b.data();
+    in.crossbuf = cb.data(); in.diag = diag.data();
+    bos::PairQueryOut o;
+    o.cross = cross; o.projected = projected; o.cov_a = cov_a; o.cov_b = cov_b;
+    for (int64_t q = 0; q < n_pairs; ++q) bos::pair_cov_query(in, o, q);
+    return BOS_OK;
+}
+
+int bos_plan_pair_paths(const bos_problem* pb, const bos_options* options, int64_t n_pairs, const int32_t* node_a,
+                        const int32_t* node_b, int32_t* out) {
+    if (!pb || n_pairs < 0 || (n_pairs > 0 && (!node_a || !node_b || !out))) return hfail(BOS_ERR_INVALID, "bad argument");
+    if (n_pairs == 0) return BOS_OK;
+    if (!bos::pair_ids_valid(pb->num_poses, pb->num_landmarks, n_pairs, node_a, node_b))
+        return hfail(BOS_ERR_INVALID, "bos_pair_covariances: a node id outside [0, NP + NL), or a mixed pair not written (pose, landmark)");
+    bos::ProblemIndex pi;
+    bos::Plan P;
+    bos::PairPaths pp;
+    const int rc = pair_plan(pb, options, pi, P, pp);
+    if (rc) return rc;
+    for (int64_t q = 0; q < n_pairs; ++q) {
+        const int a = node_a[q], b = node_b[q], sa = a == P.fixed ? -1 : pp.node_sn[a], sb = b == P.fixed ? -1 : pp.node_sn[b];
+        int32_t* o = out + 5 * q;
+        o[0] = sa; o[1] = sb;
+        o[2] = sa < 0 || sb < 0 ? -2 : bos::pair_lca(pp, sa, sb);
+        o[3] = o[2] >= 0 ? (int32_t)pp.path_dofs[o[2]] : 0;
+        o[4] = (int32_t)std::max(sa >= 0 ? pp.path_dofs[sa] : 0, sb >= 0 ? pp.path_dofs[sb] : 0);
+    }
     return BOS_OK;
 }
 

@@ -81,6 +81,19 @@ BOS_UNROLL
         }
 }
 
+// Covariance of l_a - l_b for two landmarks, J = [I, -I], C = Sigma(a, b): S_aa + S_bb - C - C^T, the
+// lower triangle, mirrored
+BOS_HD void edge_landmark_diff_cov(const double Saa[4], const double Sbb[4], const double C[4], double out[4]) {
+BOS_UNROLL
+    for (int u = 0; u < 2; ++u)
+BOS_UNROLL
+        for (int v = 0; v <= u; ++v) {
+            const double acc = Saa[2 * u + v] + Sbb[2 * u + v] - C[2 * u + v] - C[2 * v + u];
+            out[2 * u + v] = acc;
+            out[2 * v + u] = acc;
+        }
+}
+
 // bearing e: its cross block Sigma(pose, landmark) (3 x 2) and its variance
 BOS_HD void edge_cov_bearing(const EdgeCovIn& in, const EdgeCovOut& o, int64_t e) {
     const int64_t p = in.b_pose[e], l = in.b_lm[e], slot = in.edge_slot[e];
