@@ -286,3 +286,231 @@ def solver_world(name):
             P = bos.synthetic(*w, seed=5)
         _solver_world_cache[name] = (P, solver, leaf)
     return _solver_world_cache[name]
+
+
+# ---------------------------------------------------------------- 50-digit references (mpmath)
+EPS = 2.220446049250313e-16
+MP_DIGITS = 50
+
+
+def _mp():
+    import mpmath
+    mpmath.mp.dps = MP_DIGITS
+    return mpmath
+
+
+def landmark_observations(P):
+    """Per landmark, its bearings' indices in file order (what bos_create's CSR build must produce)."""
+    order = np.argsort(P.b_lm, kind="stable")
+    ptr = np.concatenate([[0], np.cumsum(np.bincount(P.b_lm, minlength=P.NL))])
+    return [order[ptr[l]:ptr[l + 1]] for l in range(P.NL)]
+
+
+def mp_triangulate(P, pose_xyt):
+    """The triangulation of every landmark from the exact double inputs, at 50 digits: the rows
+    [sin(th + z), -cos(th + z)] and right-hand sides sin(th + z) px - cos(th + z) py of
+    slam/triangulation.cpp, then per landmark a dict with
+      M, n0, n1          the number of rows and the two squared column norms,
+      basic              the two basic solutions ((c0.r / n0, 0), (0, c1.r / n1)), None where the column is 0,
+      xy, kappa          the least-squares solution (normal equations) and kappa_2 of the rows from the
+                         2 x 2 Gram matrix; None for M < 2 or a Gram determinant of 0,
+      pmax               max |p_xy| over the landmark's poses.
+    All numbers are mpmath values."""
+    mp = _mp()
+    sc = {}
+    out = []
+    for ks in landmark_observations(P):
+        n0 = n1 = g = b0 = b1 = mp.mpf(0)
+        pmax = 0.0
+        for k in ks:
+            p = pose_xyt[P.b_pose[k]]
+            key = (float(p[2]), float(P.b_z[k]))
+            if key not in sc:
+                ang = mp.mpf(key[0]) + mp.mpf(key[1])
+                sc[key] = (mp.sin(ang), mp.cos(ang))
+            s, c = sc[key]
+            a0, a1 = s, -c
+            r = s * mp.mpf(float(p[0])) - c * mp.mpf(float(p[1]))
+            n0, n1, g, b0, b1 = n0 + a0 * a0, n1 + a1 * a1, g + a0 * a1, b0 + a0 * r, b1 + a1 * r
+            pmax = max(pmax, abs(float(p[0])), abs(float(p[1])))
+        d = dict(M=len(ks), n0=n0, n1=n1, pmax=pmax, xy=None, kappa=None,
+                 basic=((b0 / n0, mp.mpf(0)) if n0 > 0 else None, (mp.mpf(0), b1 / n1) if n1 > 0 else None))
+        det = n0 * n1 - g * g
+        if len(ks) >= 2 and det > 0:
+            d["xy"] = ((n1 * b0 - g * b1) / det, (n0 * b1 - g * b0) / det)
+            lmax = (n0 + n1 + mp.sqrt((n0 - n1) ** 2 + 4 * g * g)) / 2
+            d["kappa"] = mp.sqrt(lmax / (det / lmax))
+        out.append(d)
+    return out
+
+
+def mp_boxplus(pose0, dpose):
+    """The left-multiplicative box-plus of every pose at 50 digits from the exact doubles:
+    x' = cos(dth) x - sin(dth) y + dx, y' = sin(dth) x + cos(dth) y + dy, th' = th + dth (not wrapped).
+    Returns a list of (x', y', th') mpmath triples."""
+    mp = _mp()
+    out = []
+    for (x, y, th), (dx, dy, dth) in zip(pose0, dpose):
+        x, y, th, dx, dy, dth = (mp.mpf(float(v)) for v in (x, y, th, dx, dy, dth))
+        c, s = mp.cos(dth), mp.sin(dth)
+        out.append((c * x - s * y + dx, s * x + c * y + dy, th + dth))
+    return out
+
+
+def chain_problem(pose_xyt, NL, b_pose, b_lm, b_z, lm_xy=None, odom_noise=None):
+    """A valid bos.Problem over given poses and bearings: an odometry chain 0-1-2-... measured with
+    O.predict_odometry (plus odom_noise, [NP - 1, 3]), the datasets' information, pose 0 fixed."""
+    pose_xyt = np.ascontiguousarray(pose_xyt, dtype=np.float64)
+    NP = len(pose_xyt)
+    o_z = np.array([O.predict_odometry(pose_xyt[i], pose_xyt[i + 1]) for i in range(NP - 1)])
+    if odom_noise is not None:
+        o_z = o_z + odom_noise
+    om = np.tile(np.diag([500.0, 500.0, 5000.0]), (NP - 1, 1, 1))
+    return bos.Problem(pose_xyt, np.zeros((NL, 2)) if lm_xy is None else lm_xy, b_pose, b_lm, b_z,
+                       np.arange(NP - 1, dtype=np.int32), np.arange(1, NP, dtype=np.int32), o_z, om, 0)
+
+
+def _wrap(a):
+    """a into [-pi, pi) (doubles; the world builders only)."""
+    return (a + np.pi) % (2 * np.pi) - np.pi
+
+
+def triangulation_case_world(seed=7):
+    """The hand-made world of tests/test_gpu_triangulation_edges.py: (P, kinds). Every landmark is one
+    case, kinds[l] = (kind, tag):
+      rank2      M poses at distances 2-10 from the landmark within an angular spread (tag: set, spread,
+                 M); sets: "plain", "far" (everything moved by (1e4, -1e4)), "wide+" / "wide-" (headings
+                 with th + z in (pi, 2 pi) / (-2 pi, -pi)), "pool" (2-6 poses of a shared pool)
+      one        a single observation (tag: "zero", "half_pi" or "random")
+      none       no observation (the last landmark is one)
+      par_a      exactly parallel rows, z in {0, pi/2, pi/4, 0.3}, M in {2, 3, 8}: poses with th = 0
+      par_b      exactly parallel rows, z uniform in (-pi, pi), M in {2, 3, 7, 16}
+      twice      one pose seen twice with two different z (rank 2: the pose's own position)
+      twice_same one pose seen twice with the same z (exactly parallel)
+    The bearings are in shuffled file order (the landmarks' lists interleave)."""
+    rng = np.random.default_rng(seed)
+    poses = [(0.0, 0.0, 0.0)]
+    lms = []   # (kind, tag, [(pose, z)])
+
+    def graded(name, spread, M):
+        off = np.array([1e4, -1e4]) if name == "far" else np.zeros(2)
+        L = rng.uniform(-5, 5, 2) + off
+        # phi: direction pose -> landmark; psi = phi + pi: landmark -> pose
+        phi0 = {"wide+": rng.uniform(-np.pi + 0.8, -0.8), "wide-": rng.uniform(0.8, np.pi - 0.8)}.get(
+            name, rng.uniform(-np.pi, np.pi))
+        u = rng.uniform(-0.5, 0.5, M)
+        u[0], u[1] = -0.5, 0.5
+        obs = []
+        for i in range(M):
+            psi, d = phi0 + np.pi + spread * u[i], rng.uniform(2, 10)
+            p = L + d * np.array([np.cos(psi), np.sin(psi)])
+            phi = np.arctan2(L[1] - p[1], L[0] - p[0])
+            noise = 1e-3 * spread * rng.normal()
+            if name == "wide+":      # th + z = phi + 2 pi in (pi, 2 pi)
+                th = rng.uniform(phi + np.pi + 0.1, np.pi - 0.05)
+                z = phi + 2 * np.pi - th + noise
+            elif name == "wide-":    # th + z = phi - 2 pi in (-2 pi, -pi)
+                th = rng.uniform(-np.pi + 0.05, phi - np.pi - 0.1)
+                z = phi - 2 * np.pi - th + noise
+            else:
+                th = rng.uniform(-np.pi, np.pi)
+                z = _wrap(phi - th + noise)
+            assert -np.pi < z < np.pi and -np.pi <= th < np.pi
+            poses.append((p[0], p[1], th))
+            obs.append((len(poses) - 1, z))
+        lms.append(("rank2", (name, spread, M), obs))
+
+    for name in ("plain", "far", "wide+", "wide-"):
+        for spread in (1.0, 1e-2, 1e-4, 1e-6):
+            for M in (2, 3, 5, 17, 64, 65):
+                graded(name, spread, M)
+    # shared pool: random headings, landmarks seen by 2-6 of its poses
+    pool = []
+    for _ in range(40):
+        poses.append((rng.uniform(-10, 10), rng.uniform(-10, 10), rng.uniform(-np.pi, np.pi)))
+        pool.append(len(poses) - 1)
+    for _ in range(110):
+        L = rng.uniform(-15, 15, 2)
+        obs = []
+        for i in rng.choice(pool, rng.integers(2, 7), replace=False):
+            x, y, th = poses[i]
+            obs.append((int(i), _wrap(np.arctan2(L[1] - y, L[0] - x) - th + 1e-3 * rng.normal())))
+        lms.append(("rank2", ("pool", 0.0, len(obs)), obs))
+    # one observation
+    for tag, th, z in [("zero", 0.0, 0.0), ("half_pi", 0.0, np.pi / 2)] + [("random", None, None)] * 10:
+        if th is None:
+            th, z = rng.uniform(-np.pi, np.pi), rng.uniform(-np.pi, np.pi)
+        poses.append((rng.uniform(-10, 10), rng.uniform(-10, 10), th))
+        lms.append(("one", tag, [(len(poses) - 1, z)]))
+    # exactly parallel: 16 poses with th = 0 at different places, each landmark one z from the first M
+    par = []
+    for _ in range(16):
+        poses.append((rng.uniform(-10, 10), rng.uniform(-10, 10), 0.0))
+        par.append(len(poses) - 1)
+    for z in (0.0, np.pi / 2, np.pi / 4, 0.3):
+        for M in (2, 3, 8):
+            lms.append(("par_a", (z, M), [(i, z) for i in par[:M]]))
+    zb = np.random.default_rng(1234).uniform(-np.pi, np.pi, 64)
+    for j, z in enumerate(zb):
+        M = (2, 3, 7, 16)[j % 4]
+        lms.append(("par_b", (float(z), M), [(i, float(z)) for i in par[:M]]))
+    # one pose seen twice
+    for dz in (1.0, 0.01, -2.0):
+        i, z = int(rng.choice(pool)), rng.uniform(-1, 1)
+        lms.append(("twice", dz, [(i, z), (i, z + dz)]))
+    for _ in range(3):
+        i, z = int(rng.choice(pool)), rng.uniform(-np.pi, np.pi)
+        lms.append(("twice_same", None, [(i, z), (i, z)]))
+    # no observation: three among the others, one last
+    for _ in range(3):
+        lms.append(("none", None, []))
+    order = rng.permutation(len(lms))
+    lms = [lms[i] for i in order] + [("none", None, [])]
+    b = [(p, l, z) for l, (_, _, obs) in enumerate(lms) for p, z in obs]
+    b = [b[i] for i in rng.permutation(len(b))]
+    P = chain_problem(np.array(poses), len(lms), [p for p, _, _ in b], [l for _, l, _ in b], [z for _, _, z in b])
+    return P, [(k, t) for k, t, _ in lms]
+
+
+def corridor_world(seed=3, NP=300, sigma_z=1e-3, sigma_x0=0.02):
+    """Poses one metre apart on the x axis whose true headings alternate between pi - 1e-3 and
+    -pi + 1e-3, landmarks at y = +-3 each seen by 6 consecutive poses; measurements are the ground
+    truth's predictions plus N(0, sigma_z), the initial guess the ground truth plus N(0, sigma_x0) on
+    every component (theta wrapped into [-pi, pi)), pose 0 fixed at its ground truth. With sigma_x0
+    twenty times the 1e-3 the headings keep from the wrap, about half the poses start on the far side
+    of +-pi and one GN step brings them back across it."""
+    rng = np.random.default_rng(seed)
+    gt = np.zeros((NP, 3))
+    gt[:, 0] = np.arange(NP)
+    gt[0::2, 2] = np.pi - 1e-3
+    gt[1::2, 2] = -np.pi + 1e-3
+    NL = NP // 2
+    gl = np.stack([2.0 * np.arange(NL) + 0.5, np.where(np.arange(NL) % 2 == 0, 3.0, -3.0)], axis=1)
+    bp, bl = [], []
+    for j in range(NL):
+        for i in range(2 * j - 2, 2 * j + 4):
+            if 0 <= i < NP:
+                bp.append(i)
+                bl.append(j)
+    bz = np.array([O.predict_bearing(gt[i], gl[j]) for i, j in zip(bp, bl)]) + rng.normal(0, sigma_z, len(bp))
+    x0 = gt + rng.normal(0, sigma_x0, gt.shape)
+    x0[:, 2] = _wrap(x0[:, 2])
+    x0[0] = gt[0]
+    l0 = gl + rng.normal(0, sigma_x0, gl.shape)
+    P = chain_problem(gt, NL, bp, bl, bz, odom_noise=rng.normal(0, sigma_z, (NP - 1, 3)))
+    P.pose_xyt[:] = x0
+    P.lm_xy[:] = l0
+    P.gt_pose_xyt, P.gt_lm_xy = gt, gl
+    return P
+
+
+def rotated_world(P, alpha):
+    """P turned rigidly by alpha about the origin: positions rotated, alpha added to the headings
+    (wrapped); the measurements are relative and stay."""
+    c, s = np.cos(alpha), np.sin(alpha)
+    R = np.array([[c, -s], [s, c]])
+    pose = P.pose_xyt.copy()
+    pose[:, :2] = pose[:, :2] @ R.T
+    pose[:, 2] = _wrap(pose[:, 2] + alpha)
+    return bos.Problem(pose, P.lm_xy @ R.T, P.b_pose, P.b_lm, P.b_z, P.o_src, P.o_dst, P.o_z, P.o_omega, P.fixed,
+                       b_omega=P.b_omega)
