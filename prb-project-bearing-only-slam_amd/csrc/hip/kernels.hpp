@@ -156,7 +156,7 @@ template <typename T> struct TriParams {
     T* lc;                    // [NL][2] out: T-precision cache
 };
 
-// Exchange of the sharded J+H results (hip/solver_capi.hip enqueue_exchange): copies of contiguous
+// Exchange of the sharded J+H results (hip/solver_shard.hip shard_enqueue): copies of contiguous
 // segments between the block array (kind 0), b (1), the packed send buffer (2) and the all-gather
 // receive buffer (3).
 struct ExSeg {
@@ -190,7 +190,7 @@ template <typename T>
 hipError_t launch_linearize(const LinParams<T>& p, int lpp, bool has_w, bool has_dups, hipStream_t s);
 template <typename T> hipError_t launch_boxplus(const UpdateParams<T>& p, hipStream_t s);
 
-// Sharded GN step (host/plan.hpp Shard, hip/solver_capi.hip). Exchange buffers are doubles with a
+// Sharded GN step (host/plan.hpp Shard, hip/solver_shard.hip). Exchange buffers are doubles with a
 // kExHeader-double header per rank.
 constexpr int kExHeader = 2;   // = bos::kExHeader (host/plan.hpp)
 // Exchange 1 header: this rank's chi^2 and robust count (sums of the J+H partials [0, n_parts));

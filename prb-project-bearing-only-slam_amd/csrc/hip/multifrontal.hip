@@ -28,6 +28,7 @@
 
 #include "../../../include/bos_host.h"
 #include "../host/plan.hpp"
+#include "device_mem.hpp"
 #include "multifrontal.hpp"
 #include "selinv.hpp"
 
@@ -516,7 +517,7 @@ struct ChunkTable {
     int base, v;
     __device__ __forceinline__ void load(const MfArgs& a, int b, int lane) {
         base = b;
-        v = a.fold_chunk[b + lane];   // padded array (up()): in bounds
+        v = a.fold_chunk[b + lane];   // padded array (kMfPad): in bounds
     }
     // the same inside the chunk loop, waited for on the spot: a load left pending on this rarely taken
     // path would make the compiler wait for every outstanding load at the loop's top on every path
@@ -1295,7 +1296,7 @@ struct ChildPre {
 };
 
 // (Every structure and value array is padded by kMfPad elements, so the clamped reads below stay in
-// bounds even for an empty child range; see up().)
+// bounds even for an empty child range; see kMfPad.)
 __device__ __forceinline__ void child_meta(const MfArgs& a, int c, int lane, ChildPre& p) {
     const int rc = a.r[c];   // rc < m <= MAXM
     const int roff = a.rmap_off[c];
@@ -2243,18 +2244,6 @@ __global__ __launch_bounds__(64) void mf_backward_flow(const MfArgs a, const Flo
 // unconditionally (branch-free loads, see assemble_wave) and may touch up to one chunk / 64 lanes past
 // a range's last element.
 constexpr int64_t kMfPad = 64;
-template <typename X> int up(X** p, const std::vector<X>& v, std::string& err) {
-    *p = nullptr;
-    if (v.empty()) return 0;
-    const size_t bytes = v.size() * sizeof(X), padded = bytes + kMfPad * sizeof(X);
-    if (hipMalloc((void**)p, padded) != hipSuccess) { err = "hipMalloc failed (multifrontal)"; return -2; }
-    if (hipMemcpy(*p, v.data(), bytes, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemset((char*)*p + bytes, 0, padded - bytes) != hipSuccess) {
-        err = "hipMemcpy failed (multifrontal)";
-        return -2;
-    }
-    return 0;
-}
 
 }  // namespace
 
@@ -2335,6 +2324,7 @@ constexpr int kFlowWavesBackward = BOS_MF_FLOW_WAVES_B;
 constexpr int kSolveWideLevel = BOS_MF_SOLVE_WIDE;
 constexpr int kFactorWideLevel = BOS_MF_FACTOR_WIDE;
 struct MfDevice {
+    DeviceMem mem;                // every device array below, both programs' lists included
     int nlevels = 0, nsuper = 0, ncu = 256;
     bool mixb = false;            // mf_factor_mixb too (a level's blocked and wave fronts in one launch)
     bool blk = false;             // mf_factor_blk may take its (up to 132 KB of) dynamic LDS
@@ -2406,7 +2396,7 @@ struct MfDevice {
 
 namespace {
 
-int build_prog(const Multifrontal& F, const std::vector<int8_t>& sel, int id, Prog& P, std::vector<int8_t>& fid_f,
+int build_prog(DeviceMem& mem, const Multifrontal& F, const std::vector<int8_t>& sel, int id, Prog& P, std::vector<int8_t>& fid_f,
                std::vector<int8_t>& fid_b, std::string& err) {
     P.id = id;
     const int L = F.nlevels;
@@ -2508,18 +2498,13 @@ int build_prog(const Multifrontal& F, const std::vector<int8_t>& sel, int id, Pr
     for (int s : F.fold_list)
         if (mine(F.parent[s])) folds.push_back(s);
     P.n_fold = (int)folds.size();
-    int rc;
-    if ((rc = up(&P.list, lst, err)) || (rc = up(&P.order_factor, ofac, err)) || (rc = up(&P.order_bwd, obwd, err)) ||
-        (rc = up(&P.fold_list, folds, err)) || (rc = up(&P.blist, blst, err)))
-        return rc;
+    if (!(mem.upload(&P.list, lst, kMfPad) && mem.upload(&P.order_factor, ofac, kMfPad) && mem.upload(&P.order_bwd, obwd, kMfPad) &&
+          mem.upload(&P.fold_list, folds, kMfPad) && mem.upload(&P.blist, blst, kMfPad))) {
+        err = "device allocation or upload failed (multifrontal)";
+        return -2;
+    }
     P.h_list = lst; P.h_order_factor = ofac; P.h_order_bwd = obwd; P.h_fold_list = folds; P.h_blist = blst;
     return 0;
-}
-
-void free_prog(Prog& P) {
-    void* bufs[] = {P.list, P.order_factor, P.order_bwd, P.fold_list, P.blist};
-    for (void* b : bufs)
-        if (b) (void)hipFree(b);
 }
 
 }  // namespace
@@ -2568,11 +2553,14 @@ int mf_create(const Multifrontal& F, const int8_t* owner, int rank, MfDevice** o
     if (owner)
         for (int s = 0; s < F.nsuper; ++s) sel[s] = owner[s] == rank ? 1 : owner[s] == -1 ? 2 : 0;
     int rc;
-    if ((rc = build_prog(F, sel, 1, d->prog[0], fid_f, fid_b, err)) ||
-        (owner && (rc = build_prog(F, sel, 2, d->prog[1], fid_f, fid_b, err))))
+    if ((rc = build_prog(d->mem, F, sel, 1, d->prog[0], fid_f, fid_b, err)) ||
+        (owner && (rc = build_prog(d->mem, F, sel, 2, d->prog[1], fid_f, fid_b, err))))
         return rc;
-    if ((rc = up(&d->fid_f, fid_f, err)) || (rc = up(&d->fid_b, fid_b, err)) || (rc = up(&d->parent, F.parent, err)))
-        return rc;
+    // every structure array with its kMfPad tail; every buffer zeroed
+    DeviceMem& mem = d->mem;
+    auto up = [&](auto** p, const auto& v) { return mem.upload(p, v, kMfPad); };
+    auto bad = [&] { err = "device allocation or upload failed (multifrontal)"; return -2; };
+    if (!(up(&d->fid_f, fid_f) && up(&d->fid_b, fid_b) && up(&d->parent, F.parent))) return bad();
     {   // tagged hand-offs: a flow front whose parent is in the same flow publishes its update matrix
         // and u-vector as granule pairs; every ancestor of a backward-flow front publishes its x so
         std::vector<int64_t> ugo(F.nsuper, -1);
@@ -2589,31 +2577,11 @@ int mf_create(const Multifrontal& F, const int8_t* owner, int rank, MfDevice** o
         for (int c = 0; c < F.nsuper; ++c)
             if (fid_b[c] != 0)
                 for (int q = c; q >= 0 && !xt[q]; q = F.parent[q]) xt[q] = 1;
-        if ((rc = up(&d->ug_off, ugo, err)) || (rc = up(&d->xtag, xt, err))) return rc;
-        auto alloc0 = [&](unsigned long long** p, int64_t n) -> int {
-            n = std::max<int64_t>(n, 1) + 2 * kMfPad;
-            if (hipMalloc((void**)p, n * sizeof(unsigned long long)) != hipSuccess ||
-                hipMemset(*p, 0, n * sizeof(unsigned long long)) != hipSuccess) {
-                err = "hipMalloc failed (multifrontal granules)";
-                return -2;
-            }
-            return 0;
-        };
-        if ((rc = alloc0(&d->Ug, ug_size)) || (rc = alloc0(&d->xg, 2 * ndof))) return rc;
+        if (!(up(&d->ug_off, ugo) && up(&d->xtag, xt) && mem.alloc(&d->Ug, std::max<int64_t>(ug_size, 1), true, 2 * kMfPad) &&
+              mem.alloc(&d->xg, std::max<int64_t>(2 * ndof, 1), true, 2 * kMfPad)))
+            return bad();
     }
-    if (hipMalloc((void**)&d->tickets, 2 * kMfTickets * sizeof(int)) != hipSuccess ||
-        hipMemset(d->tickets, 0, 2 * kMfTickets * sizeof(int)) != hipSuccess ||
-        hipMalloc((void**)&d->epoch, sizeof(uint32_t)) != hipSuccess) {
-        err = "hipMalloc failed (multifrontal flow)";
-        return -2;
-    }
-    {
-        const uint32_t one = 1;
-        if (hipMemcpy(d->epoch, &one, sizeof(one), hipMemcpyHostToDevice) != hipSuccess) {
-            err = "hipMemcpy failed (multifrontal epoch)";
-            return -2;
-        }
-    }
+    if (!(mem.alloc(&d->tickets, 2 * kMfTickets, true) && mem.upload(&d->epoch, std::vector<uint32_t>{1}))) return bad();
     {   // extend-add positions of every child whose parent is a wave or blocked front (m <= kBlkMaxM)
         std::vector<int64_t> eoff(F.nsuper, 0);
         std::vector<int16_t> em;
@@ -2636,18 +2604,15 @@ int mf_create(const Multifrontal& F, const int8_t* owner, int rank, MfDevice** o
                     em.push_back((int16_t)(mp <= kMfWaveMaxM ? J * mp - J * (J - 1) / 2 + (I - J) : I + J * mp));
                 }
         }
-        if ((rc = up(&d->emap, em, err)) || (rc = up(&d->emap_off, eoff, err))) return rc;
+        if (!(up(&d->emap, em) && up(&d->emap_off, eoff))) return bad();
     }
-    if ((rc = up(&d->col0, F.col0, err)) || (rc = up(&d->k, F.k, err)) ||
-        (rc = up(&d->r, F.r, err)) || (rc = up(&d->child_ptr, F.child_ptr, err)) || (rc = up(&d->child, F.child, err)) ||
-        (rc = up(&d->rmap, F.rmap, err)) || (rc = up(&d->amap_ptr, F.amap_ptr, err)) ||
-        (rc = up(&d->amap_src, F.amap_src, err)) || (rc = up(&d->amap_dst, F.amap_dst, err)) ||
-        (rc = up(&d->findex, F.findex, err)) || (rc = up(&d->L_off, F.L_off, err)) || (rc = up(&d->U_off, F.U_off, err)) ||
-        (rc = up(&d->u_off, F.u_off, err)) || (rc = up(&d->scratch_off, scr, err)) ||
-        (rc = up(&d->rmap_off, F.rmap_off, err)) || (rc = up(&d->findex_off, F.findex_off, err)) ||
-        (rc = up(&d->fold_cnt, F.fold_cnt, err)) || (rc = up(&d->fold_cptr, F.fold_cptr, err)) ||
-        (rc = up(&d->fold_chunk, F.fold_chunk, err)) || (rc = up(&d->fold_rec, F.fold_rec, err)))
-        return rc;
+    if (!(up(&d->col0, F.col0) && up(&d->k, F.k) && up(&d->r, F.r) && up(&d->child_ptr, F.child_ptr) && up(&d->child, F.child) &&
+          up(&d->rmap, F.rmap) && up(&d->amap_ptr, F.amap_ptr) && up(&d->amap_src, F.amap_src) && up(&d->amap_dst, F.amap_dst) &&
+          up(&d->findex, F.findex) && up(&d->L_off, F.L_off) && up(&d->U_off, F.U_off) && up(&d->u_off, F.u_off) &&
+          up(&d->scratch_off, scr) && up(&d->rmap_off, F.rmap_off) && up(&d->findex_off, F.findex_off) &&
+          up(&d->fold_cnt, F.fold_cnt) && up(&d->fold_cptr, F.fold_cptr) && up(&d->fold_chunk, F.fold_chunk) &&
+          up(&d->fold_rec, F.fold_rec)))
+        return bad();
     if (hipStreamCreateWithFlags(&d->side, hipStreamNonBlocking) != hipSuccess ||
         hipStreamCreateWithFlags(&d->side2, hipStreamNonBlocking) != hipSuccess ||
         hipEventCreateWithFlags(&d->ev_fork, hipEventDisableTiming) != hipSuccess ||
@@ -2656,31 +2621,18 @@ int mf_create(const Multifrontal& F, const int8_t* owner, int rank, MfDevice** o
         err = "side stream creation failed (multifrontal)";
         return -2;
     }
-    auto alloc = [&](double** p, int64_t n) -> int {   // + kMfPad: clamped reads (up())
-        if (n <= 0) n = 1;
-        if (hipMalloc((void**)p, (n + kMfPad) * sizeof(double)) != hipSuccess) { err = "hipMalloc failed (multifrontal buffers)"; return -2; }
-        if (hipMemset(*p, 0, (n + kMfPad) * sizeof(double)) != hipSuccess) { err = "hipMemset failed (multifrontal buffers)"; return -2; }
-        return 0;
+    auto alloc = [&](double** p, int64_t n) {   // + kMfPad: clamped reads
+        return mem.alloc(p, std::max<int64_t>(n, 1), true, kMfPad);
     };
-    if ((rc = alloc(&d->L, F.L_size)) || (rc = alloc(&d->U, F.U_size)) || (rc = alloc(&d->u, F.u_size)) ||
-        (rc = alloc(&d->scratch, scratch_size)))
-        return rc;
-    if (hipMalloc((void**)&d->info, sizeof(int32_t)) != hipSuccess) { err = "hipMalloc failed (info)"; return -2; }
-    if (hipMemset(d->info, 0, sizeof(int32_t)) != hipSuccess) { err = "hipMemset failed"; return -2; }
+    if (!(alloc(&d->L, F.L_size) && alloc(&d->U, F.U_size) && alloc(&d->u, F.u_size) && alloc(&d->scratch, scratch_size) &&
+          mem.alloc(&d->info, 1, true)))
+        return bad();
     return 0;
 }
 
 void mf_destroy(MfDevice* d) {
     if (!d) return;
     selinv_destroy(d->selinv);
-    free_prog(d->prog[0]);
-    free_prog(d->prog[1]);
-    void* bufs[] = {d->emap, d->emap_off, d->epoch, d->fid_f, d->fid_b, d->fold_cnt, d->fold_cptr, d->fold_chunk, d->fold_rec, d->parent,
-                    d->tickets, d->col0, d->k, d->r, d->child_ptr, d->child, d->rmap, d->amap_ptr, d->amap_src,
-                    d->amap_dst, d->findex, d->info, d->L_off, d->U_off, d->u_off, d->scratch_off, d->rmap_off,
-                    d->findex_off, d->L, d->U, d->u, d->scratch, d->Ug, d->xg, d->ug_off, d->xtag};
-    for (void* b : bufs)
-        if (b) (void)hipFree(b);
     if (d->ev_fork) (void)hipEventDestroy(d->ev_fork);
     if (d->ev_join) (void)hipEventDestroy(d->ev_join);
     if (d->ev_join2) (void)hipEventDestroy(d->ev_join2);

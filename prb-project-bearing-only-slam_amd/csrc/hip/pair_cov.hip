@@ -17,6 +17,7 @@
 // whole path, lower triangle evaluated and mirrored.
 // pair_project_kernel: one thread per query (host/pair_cov.hpp pair_cov_query).
 #include "pair_cov.hpp"
+#include "device_mem.hpp"
 
 #include <algorithm>
 
@@ -247,8 +248,8 @@ __global__ __launch_bounds__(kProjBlock) void pair_project_kernel(const PairQuer
 }  // namespace
 
 struct PairCov {
+    DeviceMem mem;           // the arena alone
     char* arena = nullptr;
-    int64_t bytes = 0;
     // the uploaded batch
     int32_t n_nodes = 0;
     int64_t n_queries = 0;
@@ -261,67 +262,43 @@ struct PairCov {
 
 PairCov* pair_cov_create() { return new PairCov(); }
 
-void pair_cov_destroy(PairCov* p) {
-    if (!p) return;
-    if (p->arena) (void)hipFree(p->arena);
-    delete p;
-}
+void pair_cov_destroy(PairCov* p) { delete p; }
 
-int64_t pair_cov_bytes(const PairCov* p) { return p ? p->bytes : 0; }
+int64_t pair_cov_bytes(const PairCov* p) { return p ? (int64_t)p->mem.bytes() : 0; }
 
 int pair_cov_upload(PairCov* p, const PairCovBatch& b, const bool want[4], std::string& err) {
     // one arena: [index arrays | Y | diagonal blocks | cross blocks | outputs], every part aligned to 256 bytes
-    int64_t bytes = 0;
-    auto take = [&](int64_t count, int64_t elem) {
-        const int64_t off = bytes;
-        bytes += (std::max<int64_t>(count, 1) * elem + 255) / 256 * 256;
-        return off;
-    };
-    const int64_t nn = b.n_nodes, nq = b.n_queries;
+    // (an empty one keeps an element's room); it only grows
+    const size_t nn = (size_t)b.n_nodes, nq = (size_t)b.n_queries;
     const bool need_diag = want[1] || want[2] || want[3], need_cross = want[0] || want[1];
-    const int64_t o_yoff = take(nn, 8), o_nsn = take(nn, 4), o_nloc = take(nn, 4), o_nd = take(nn, 4), o_nlen = take(nn, 4);
-    int64_t o_q[7];
-    for (int i = 0; i < 7; ++i) o_q[i] = take(nq, 4);
-    const int64_t o_Y = take(b.y_count, 8), o_diag = take(need_diag ? 9 * nn : 0, 8), o_cross = take(need_cross ? 9 * nq : 0, 8);
-    int64_t o_out[4];
-    for (int i = 0; i < 4; ++i) o_out[i] = take(want[i] ? 9 * nq : 0, 8);
-    if (bytes > p->bytes) {
-        if (p->arena) (void)hipFree(p->arena);
-        p->arena = nullptr;
-        p->bytes = 0;
-        if (hipMalloc((void**)&p->arena, (size_t)bytes) != hipSuccess) {
-            (void)hipGetLastError();
-            p->arena = nullptr;
-            err = "bos_pair_covariances: device allocation of " + std::to_string(bytes) + " bytes failed";
-            return -2;
-        }
-        p->bytes = bytes;
+    Arena ar(true);
+    ar.add(&p->y_off, b.y_off, nn);
+    ar.add(&p->n_sn, b.n_sn, nn); ar.add(&p->n_loc, b.n_loc, nn); ar.add(&p->n_d, b.n_d, nn); ar.add(&p->n_len, b.n_len, nn);
+    ar.add(&p->q_a, b.q_a, nq); ar.add(&p->q_b, b.q_b, nq); ar.add(&p->q_slot_a, b.q_slot_a, nq); ar.add(&p->q_slot_b, b.q_slot_b, nq);
+    ar.add(&p->q_off_a, b.q_off_a, nq); ar.add(&p->q_off_b, b.q_off_b, nq); ar.add(&p->q_c, b.q_c, nq);
+    ar.reserve(&p->Y, (size_t)b.y_count);
+    ar.reserve(&p->diag, need_diag ? 9 * nn : 0);
+    ar.reserve(&p->cross, need_cross ? 9 * nq : 0);
+    for (int i = 0; i < 4; ++i) ar.reserve(&p->out[i], want[i] ? 9 * nq : 0);
+    bool ok;
+    if (ar.bytes() > p->mem.bytes()) {
+        p->mem.release(p->arena);
+        ok = ar.commit(p->mem, &p->arena);
+    } else {
+        ok = ar.place(p->arena);
     }
-    char* A = p->arena;
-    auto up = [&](int64_t off, const void* src, int64_t count, int64_t elem) {
-        return count == 0 || hipMemcpy(A + off, src, (size_t)(count * elem), hipMemcpyHostToDevice) == hipSuccess;
-    };
-    const int32_t* qs[7] = {b.q_a, b.q_b, b.q_slot_a, b.q_slot_b, b.q_off_a, b.q_off_b, b.q_c};
-    bool ok = up(o_yoff, b.y_off, nn, 8) && up(o_nsn, b.n_sn, nn, 4) && up(o_nloc, b.n_loc, nn, 4) && up(o_nd, b.n_d, nn, 4) &&
-              up(o_nlen, b.n_len, nn, 4);
-    for (int i = 0; i < 7 && ok; ++i) ok = up(o_q[i], qs[i], nq, 4);
     if (!ok) {
-        (void)hipGetLastError();
-        err = "bos_pair_covariances: upload of the batch failed";
+        err = "bos_pair_covariances: device allocation or upload of " + std::to_string(ar.bytes()) + " bytes failed";
         return -2;
     }
     p->n_nodes = b.n_nodes;
-    p->n_queries = nq;
-    for (int i = 0; i < 4; ++i) p->want[i] = want[i];
-    p->y_off = (int64_t*)(A + o_yoff);
-    p->n_sn = (int32_t*)(A + o_nsn); p->n_loc = (int32_t*)(A + o_nloc); p->n_d = (int32_t*)(A + o_nd); p->n_len = (int32_t*)(A + o_nlen);
-    p->q_a = (int32_t*)(A + o_q[0]); p->q_b = (int32_t*)(A + o_q[1]); p->q_slot_a = (int32_t*)(A + o_q[2]);
-    p->q_slot_b = (int32_t*)(A + o_q[3]); p->q_off_a = (int32_t*)(A + o_q[4]); p->q_off_b = (int32_t*)(A + o_q[5]);
-    p->q_c = (int32_t*)(A + o_q[6]);
-    p->Y = (double*)(A + o_Y);
-    p->diag = need_diag ? (double*)(A + o_diag) : nullptr;
-    p->cross = need_cross ? (double*)(A + o_cross) : nullptr;
-    for (int i = 0; i < 4; ++i) p->out[i] = want[i] ? (double*)(A + o_out[i]) : nullptr;
+    p->n_queries = b.n_queries;
+    for (int i = 0; i < 4; ++i) {
+        p->want[i] = want[i];
+        if (!want[i]) p->out[i] = nullptr;
+    }
+    if (!need_diag) p->diag = nullptr;
+    if (!need_cross) p->cross = nullptr;
     return 0;
 }
 

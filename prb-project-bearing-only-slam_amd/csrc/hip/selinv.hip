@@ -25,10 +25,12 @@
 #include "selinv.hpp"
 
 #include <algorithm>
+#include <memory>
 #include <vector>
 
 #include "../../../include/bos_host.h"
 #include "../host/plan.hpp"
+#include "device_mem.hpp"
 #include "edge_cov.hpp"
 #include "multifrontal.hpp"
 
@@ -181,19 +183,13 @@ struct Launch {
     int first, count, threads, lds;
 };
 
-template <typename X> bool put(X** p, const std::vector<X>& v, int64_t& bytes) {
-    *p = nullptr;
-    bytes = (int64_t)std::max<size_t>(v.size(), 1) * sizeof(X);
-    if (hipMalloc((void**)p, bytes) != hipSuccess) { *p = nullptr; return false; }
-    return v.empty() || hipMemcpy(*p, v.data(), v.size() * sizeof(X), hipMemcpyHostToDevice) == hipSuccess;
-}
-
 }  // namespace
 
 // the feature's state (mf_edge_cov_build): index arrays, pair buffer and per-edge outputs in one arena
 struct EdgeCovDev {
-    char* arena = nullptr;
-    int64_t bytes = 0, n_pairs = 0;
+    DeviceMem mem;           // the arena alone
+    char* arena = nullptr;   // null until built
+    int64_t n_pairs = 0;
     int Mb = 0, Mo = 0;
     int32_t *cr_ptr = nullptr, *cr_rec = nullptr, *edge_slot = nullptr, *edge_tr = nullptr;
     int32_t *b_pose = nullptr, *b_lm = nullptr, *o_src = nullptr, *o_dst = nullptr;
@@ -202,6 +198,7 @@ struct EdgeCovDev {
 };
 
 struct SelInv {
+    DeviceMem mem;   // every device array below (the edge arena: ec.mem)
     EdgeCovDev ec;
     std::vector<Launch> launches;
     // the report (mf_selinv_report): per supernode the class and the launch selinv_build's add gave it,
@@ -215,14 +212,7 @@ struct SelInv {
     int64_t sigma_bytes = 0, out_count = 0, lm_base = 0;
 };
 
-void selinv_destroy(SelInv* p) {
-    if (!p) return;
-    void* bufs[] = {p->list, p->out_ptr, p->out_rec, p->S_off, p->ws_off, p->S, p->ws, p->out};
-    for (void* b : bufs)
-        if (b) (void)hipFree(b);
-    if (p->ec.arena) (void)hipFree(p->ec.arena);
-    delete p;
-}
+void selinv_destroy(SelInv* p) { delete p; }
 
 namespace {
 
@@ -249,7 +239,7 @@ int selinv_build(const Plan& P, SelInv** out, std::string& err) {
     (void)hipGetLastError();
     const int lds_cap = big_lds ? blk_lds : kDefaultLds;
 
-    SelInv* si = new SelInv();
+    std::unique_ptr<SelInv> si(new SelInv());   // dropped with its allocations on every failure below
     si->cls.assign(F.nsuper, (int8_t)-1);
     si->launch_of.assign(F.nsuper, -1);
     std::vector<int32_t> list;
@@ -263,7 +253,6 @@ int selinv_build(const Plan& P, SelInv** out, std::string& err) {
         }
     for (int s = 0; s < F.nsuper; ++s)
         if (F.r[s] > 0 && S_off[F.parent[s]] < 0) {
-            delete si;
             err = "marginals: a supernode is missing from its parent's child list";
             return -1;
         }
@@ -307,23 +296,19 @@ int selinv_build(const Plan& P, SelInv** out, std::string& err) {
     si->lm_base = 9 * (int64_t)P.NP;
     si->out_count = 9 * (int64_t)P.NP + 4 * (int64_t)P.NL;
     si->sigma_bytes = std::max<int64_t>(S_size, 1) * (int64_t)sizeof(double);
-    int64_t bytes = 0;
-    bool ok = put(&si->list, list, bytes) && put(&si->out_ptr, out_ptr, bytes) && put(&si->out_rec, out_rec, bytes) &&
-              put(&si->S_off, S_off, bytes) && put(&si->ws_off, ws_off, bytes);
-    if (ok) { bytes = si->sigma_bytes; ok = hipMalloc((void**)&si->S, bytes) == hipSuccess; if (!ok) si->S = nullptr; }
-    if (ok) { bytes = std::max<int64_t>(ws_size, 1) * (int64_t)sizeof(double); ok = hipMalloc((void**)&si->ws, bytes) == hipSuccess; if (!ok) si->ws = nullptr; }
-    if (ok) { bytes = std::max<int64_t>(si->out_count, 1) * (int64_t)sizeof(double); ok = hipMalloc((void**)&si->out, bytes) == hipSuccess; if (!ok) si->out = nullptr; }
+    DeviceMem& mem = si->mem;
+    if (!(mem.upload(&si->list, list, 0, true) && mem.upload(&si->out_ptr, out_ptr, 0, true) &&
+          mem.upload(&si->out_rec, out_rec, 0, true) && mem.upload(&si->S_off, S_off, 0, true) &&
+          mem.upload(&si->ws_off, ws_off, 0, true) && mem.alloc(&si->S, std::max<int64_t>(S_size, 1), false) &&
+          mem.alloc(&si->ws, std::max<int64_t>(ws_size, 1), false) && mem.alloc(&si->out, std::max<int64_t>(si->out_count, 1), false))) {
+        err = "marginals: a device allocation failed after " + std::to_string(mem.bytes()) +
+              " bytes (Sigma-front buffer: " + std::to_string(si->sigma_bytes) + " bytes)";
+        return -2;
+    }
     si->h_out_ptr.swap(out_ptr);
     si->h_out_rec.swap(out_rec);
     si->h_S_off.swap(S_off);
-    if (!ok) {
-        (void)hipGetLastError();
-        err = "marginals: device allocation of " + std::to_string(bytes) + " bytes failed (Sigma-front buffer: " +
-              std::to_string(si->sigma_bytes) + " bytes)";
-        selinv_destroy(si);
-        return -2;
-    }
-    *out = si;
+    *out = si.release();
     return 0;
 }
 
@@ -369,7 +354,7 @@ bool mf_edge_cov_built(const MfDevice* d) {
 
 int64_t mf_edge_cov_bytes(const MfDevice* d) {
     SelInv* const* slot = mf_selinv_slot(const_cast<MfDevice*>(d));
-    return *slot ? (*slot)->ec.bytes : 0;
+    return *slot ? (int64_t)(*slot)->ec.mem.bytes() : 0;
 }
 
 int mf_edge_cov_build(MfDevice* d, const Plan& P, const EdgeList& E, std::string& err) {
@@ -400,45 +385,23 @@ int mf_edge_cov_build(MfDevice* d, const Plan& P, const EdgeList& E, std::string
     for (int64_t e = 0; e < edges && good; ++e) good = cr.edge_slot[e] >= -1 && cr.edge_slot[e] < cr.n_pairs;
     if (!good) { err = "bos_edge_covariances: malformed cross records"; return -1; }
 
-    // one arena: [index arrays | pair buffer | per-edge outputs], every part aligned to 256 bytes
-    int64_t bytes = 0;
-    auto take = [&](int64_t count, int64_t elem) {
-        const int64_t off = bytes;
-        bytes += (std::max<int64_t>(count, 1) * elem + 255) / 256 * 256;
-        return off;
-    };
-    const int64_t o_ptr = take((int64_t)cr.ptr.size(), 4), o_rec = take((int64_t)cr.rec.size(), 4), o_slot = take(edges, 4),
-                  o_tr = take(edges, 4), o_bp = take(E.Mb, 4), o_bl = take(E.Mb, 4), o_os = take(E.Mo, 4), o_od = take(E.Mo, 4),
-                  o_pairs = take(9 * cr.n_pairs, 8), o_bc = take(6 * (int64_t)E.Mb, 8), o_oc = take(9 * (int64_t)E.Mo, 8),
-                  o_bv = take(E.Mb, 8), o_ov = take(9 * (int64_t)E.Mo, 8);
-    char* arena = nullptr;
-    if (hipMalloc((void**)&arena, (size_t)bytes) != hipSuccess) {
-        (void)hipGetLastError();
-        err = "bos_edge_covariances: device allocation of " + std::to_string(bytes) + " bytes failed";
+    // one arena: [index arrays | pair buffer | per-edge outputs], every part aligned to 256 bytes (an
+    // empty one keeps an element's room). Built aside: a failure leaves ec as it was.
+    Arena ar(true);
+    ar.add(&ec.cr_ptr, cr.ptr); ar.add(&ec.cr_rec, cr.rec); ar.add(&ec.edge_slot, cr.edge_slot); ar.add(&ec.edge_tr, cr.edge_tr);
+    ar.add(&ec.b_pose, E.b_pose, (size_t)E.Mb); ar.add(&ec.b_lm, E.b_lm, (size_t)E.Mb);
+    ar.add(&ec.o_src, E.o_src, (size_t)E.Mo); ar.add(&ec.o_dst, E.o_dst, (size_t)E.Mo);
+    ar.reserve(&ec.pairs, 9 * (size_t)cr.n_pairs);
+    ar.reserve(&ec.bearing_cross, 6 * (size_t)E.Mb); ar.reserve(&ec.odom_cross, 9 * (size_t)E.Mo);
+    ar.reserve(&ec.bearing_var, (size_t)E.Mb); ar.reserve(&ec.odom_cov, 9 * (size_t)E.Mo);
+    DeviceMem mem;
+    if (!ar.commit(mem, &ec.arena)) {
+        err = "bos_edge_covariances: device allocation or upload of " + std::to_string(ar.bytes()) + " bytes failed";
         return -2;
     }
-    auto up = [&](int64_t off, const int32_t* src, int64_t count) {
-        return count == 0 || hipMemcpy(arena + off, src, (size_t)count * sizeof(int32_t), hipMemcpyHostToDevice) == hipSuccess;
-    };
-    if (!(up(o_ptr, cr.ptr.data(), (int64_t)cr.ptr.size()) && up(o_rec, cr.rec.data(), (int64_t)cr.rec.size()) &&
-          up(o_slot, cr.edge_slot.data(), edges) && up(o_tr, cr.edge_tr.data(), edges) && up(o_bp, E.b_pose, E.Mb) &&
-          up(o_bl, E.b_lm, E.Mb) && up(o_os, E.o_src, E.Mo) && up(o_od, E.o_dst, E.Mo))) {
-        (void)hipGetLastError();
-        (void)hipFree(arena);
-        err = "bos_edge_covariances: upload of the cross records failed";
-        return -2;
-    }
-    ec.arena = arena;
-    ec.bytes = bytes;
+    ec.mem = std::move(mem);
     ec.n_pairs = cr.n_pairs;
     ec.Mb = E.Mb; ec.Mo = E.Mo;
-    ec.cr_ptr = (int32_t*)(arena + o_ptr); ec.cr_rec = (int32_t*)(arena + o_rec);
-    ec.edge_slot = (int32_t*)(arena + o_slot); ec.edge_tr = (int32_t*)(arena + o_tr);
-    ec.b_pose = (int32_t*)(arena + o_bp); ec.b_lm = (int32_t*)(arena + o_bl);
-    ec.o_src = (int32_t*)(arena + o_os); ec.o_dst = (int32_t*)(arena + o_od);
-    ec.pairs = (double*)(arena + o_pairs);
-    ec.bearing_cross = (double*)(arena + o_bc); ec.odom_cross = (double*)(arena + o_oc);
-    ec.bearing_var = (double*)(arena + o_bv); ec.odom_cov = (double*)(arena + o_ov);
     ec.h_cr = std::move(cr);
     return 0;
 }

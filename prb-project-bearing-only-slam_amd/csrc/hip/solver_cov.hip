@@ -1,0 +1,251 @@
+// Covariances from the multifrontal factor on the C ABI handle (solver_handle.hpp): marginals, edge and
+// pair covariances (hip/selinv.hpp, hip/pair_cov.hpp).
+#include <algorithm>
+#include <chrono>
+
+#include "solver_handle.hpp"
+
+using namespace bos::capi;
+
+namespace {
+
+// The feature's device state at the first bos_edge_covariances (hip/selinv.hip mf_edge_cov_build): the
+// edges in measurement order are the handle's table of the bearings' landmarks and the device copies it
+// already keeps (the bearings' poses, the odometry's endpoints)
+int edge_cov_setup(bos_solver* s) {
+    if (bos::dev::mf_edge_cov_built(s->mf)) return BOS_OK;
+    std::vector<int32_t> bp(s->Mb, 0), os(s->Mo, 0), od(s->Mo, 0);
+    const std::vector<int32_t>& bl = s->bearing_lm;
+    if (s->Mb) HIP_TRY(hipMemcpy(bp.data(), s->tri_pose, bp.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (s->Mo) {
+        HIP_TRY(hipMemcpy(os.data(), s->o_src, os.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(od.data(), s->o_dst, od.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+    }
+    bos::dev::EdgeList E;
+    E.Mb = s->Mb; E.Mo = s->Mo;
+    E.b_pose = bp.data(); E.b_lm = bl.data(); E.o_src = os.data(); E.o_dst = od.data();
+    std::string err;
+    const int rc = bos::dev::mf_edge_cov_build(s->mf, s->plan, E, err);
+    if (rc) return fail(rc == -1 ? BOS_ERR_UNSUPPORTED : BOS_ERR_DEVICE, err);
+    return BOS_OK;
+}
+
+// the factorization's word read and cleared (a step expects it zero), the stream drained
+hipError_t take_factor_info(bos_solver* s, int32_t* info) {
+    hipError_t e = hipMemcpyAsync(info, bos::dev::mf_info_ptr(s->mf), sizeof(*info), hipMemcpyDeviceToHost, s->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(bos::dev::mf_info_ptr(s->mf), 0, sizeof(int32_t), s->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
+    return e;
+}
+
+// The shared start of a covariance call: the system of bos_linearize and its factorization, as a step
+// enqueues them (bos_step returns on its status word, before the stream has drained: everything here is
+// ordered after it by the stream), between events 0, 1 and 2. With info_now the factorization's word is
+// read and cleared and the stream drained before anything reads the panels; a caller that passes null
+// takes the word later (take_factor_info).
+int enqueue_factorization(bos_solver* s, int32_t* info_now) {
+    int rc;
+    HIP_TRY(hipEventRecord(s->ev[0], s->stream));
+    if ((rc = enqueue_linearize(s))) return rc;
+    HIP_TRY(hipEventRecord(s->ev[1], s->stream));
+    if ((rc = enqueue_solver_inputs(s))) return rc;   // opens the flows' epoch, as a step does
+    HIP_TRY(bos::dev::mf_factor(s->mf, 0, mf_matrix(s), s->d_rhs, s->stream));
+    s->have_dx = false;   // d_rhs now holds L^-1 b of this factorization
+    HIP_TRY(hipEventRecord(s->ev[2], s->stream));
+    if (info_now) HIP_TRY(take_factor_info(s, info_now));
+    return BOS_OK;
+}
+
+// bos_marginals (edge = nullptr) and bos_edge_covariances (edge[4] = bearing_cross, odom_cross,
+// bearing_var, odom_cov; with all four null the pass is the marginals' own)
+int covariance_pass(bos_solver* s, const char* name, double* const* edge, double* pose_cov, double* landmark_cov,
+                    int32_t* solver_info) {
+    int rc;
+    if (!s) return fail(BOS_ERR_INVALID, "null handle");
+    if ((rc = require_one_gpu(s, name, true, " (a rank holds part of the factor)"))) return rc;
+    HIP_TRY(hipSetDevice(s->device));
+    if (solver_info) *solver_info = 0;
+    const int64_t n = s->plan.n;
+    const size_t np9 = 9 * (size_t)s->NP, nl4 = 4 * (size_t)s->NL;
+    const size_t ecount[4] = {6 * (size_t)s->Mb, 9 * (size_t)s->Mo, (size_t)s->Mb, 9 * (size_t)s->Mo};
+    bool want[4] = {false, false, false, false};
+    bool any_edge = false;
+    for (int i = 0; i < 4 && edge; ++i) any_edge |= want[i] = edge[i] != nullptr && ecount[i] > 0;
+    if (n == 0) {   // the fixed pose alone: every block and every cross block is zero
+        if (pose_cov) std::fill(pose_cov, pose_cov + np9, 0.0);
+        if (landmark_cov) std::fill(landmark_cov, landmark_cov + nl4, 0.0);
+        for (int i = 0; i < 4; ++i)
+            if (want[i]) std::fill(edge[i], edge[i] + ecount[i], 0.0);
+        return BOS_OK;
+    }
+    if (any_edge && (rc = edge_cov_setup(s))) return rc;
+    if ((rc = enqueue_factorization(s, nullptr))) return rc;
+    const double* out = nullptr;
+    std::string err;
+    int src = bos::dev::mf_selected_inverse(s->mf, s->plan, &out, s->stream, err, any_edge);
+    // the factorization's word, read and cleared whatever happened next: a step expects it zero
+    int32_t info = 0;
+    hipError_t e = hipEventRecord(s->ev[3], s->stream);
+    bos::dev::EdgeCovResult er;
+    if (any_edge && !src && e == hipSuccess) {
+        src = bos::dev::mf_edge_project(s->mf, s->d_pose, s->d_lm, want, &er, s->stream, err);
+        e = hipEventRecord(s->ev[4], s->stream);
+    }
+    if (e == hipSuccess) e = take_factor_info(s, &info);
+    HIP_TRY(e);
+    if (src) return fail(src == -1 ? BOS_ERR_UNSUPPORTED : BOS_ERR_DEVICE, err);
+    if (info & bos::dev::kMfStall)
+        return fail(BOS_ERR_SOLVER, "sparse factorization aborted: a dataflow dependency wait timed out");
+    const auto t0 = std::chrono::steady_clock::now();
+    if (pose_cov) HIP_TRY(hipMemcpy(pose_cov, out, np9 * sizeof(double), hipMemcpyDeviceToHost));
+    if (landmark_cov && nl4) HIP_TRY(hipMemcpy(landmark_cov, out + np9, nl4 * sizeof(double), hipMemcpyDeviceToHost));
+    if (any_edge) {
+        const double* dev[4] = {er.bearing_cross, er.odom_cross, er.bearing_var, er.odom_cov};
+        for (int i = 0; i < 4; ++i)
+            if (want[i]) HIP_TRY(hipMemcpy(edge[i], dev[i], ecount[i] * sizeof(double), hipMemcpyDeviceToHost));
+    }
+    const double dl = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    if (edge) {
+        for (int i = 0; i < 3; ++i) s->edge_ms[i] = elapsed(s->ev[i], s->ev[i + 1]);
+        s->edge_ms[3] = any_edge ? elapsed(s->ev[3], s->ev[4]) : 0.0;
+        s->edge_ms[4] = dl;
+    } else {
+        s->marg_ms[3] = dl;
+        for (int i = 0; i < 3; ++i) s->marg_ms[i] = elapsed(s->ev[i], s->ev[i + 1]);
+    }
+    if (solver_info) *solver_info = info;
+    return BOS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int bos_debug_selinv_fronts(bos_solver* s, int64_t capacity, int32_t* fronts, int32_t* nsuper, int32_t* node_front,
+                            int32_t* edge_front) {
+    if (!s) return fail(BOS_ERR_INVALID, "null handle");
+    if (!uses_mf(s)) return fail(BOS_ERR_UNSUPPORTED, "multifrontal handles only");
+    const bos::Multifrontal& F = s->plan.mf;
+    if (nsuper) *nsuper = F.nsuper;
+    if (!fronts && capacity == 0 && nsuper) return BOS_OK;
+    if (!fronts || capacity < (int64_t)BOS_SELINV_COLS * F.nsuper)
+        return fail(BOS_ERR_INVALID, "selinv fronts: capacity BOS_SELINV_COLS * supernodes");
+    if (bos::dev::mf_selinv_report(s->mf, s->plan, fronts, node_front, edge_front))
+        return fail(BOS_ERR_INVALID, "selinv fronts: no bos_marginals / bos_edge_covariances call has built the plan on this handle yet");
+    return BOS_OK;
+}
+
+int bos_marginals(bos_solver* s, double* pose_cov, double* landmark_cov, int32_t* solver_info) {
+    return covariance_pass(s, "bos_marginals", nullptr, pose_cov, landmark_cov, solver_info);
+}
+
+int bos_edge_covariances(bos_solver* s, double* bearing_cross, double* odom_cross, double* bearing_var, double* odom_cov,
+                         double* pose_cov, double* landmark_cov, int32_t* solver_info) {
+    double* const edge[4] = {bearing_cross, odom_cross, bearing_var, odom_cov};
+    return covariance_pass(s, "bos_edge_covariances", edge, pose_cov, landmark_cov, solver_info);
+}
+
+int bos_edge_covariances_timing(const bos_solver* s, double ms[5], int64_t* edge_bytes) {
+    if (!s || !ms) return fail(BOS_ERR_INVALID, "null argument");
+    for (int i = 0; i < 5; ++i) ms[i] = s->edge_ms[i];
+    if (edge_bytes) *edge_bytes = s->mf ? bos::dev::mf_edge_cov_bytes(s->mf) : 0;
+    return BOS_OK;
+}
+
+int bos_marginals_timing(const bos_solver* s, double ms[4], int64_t* sigma_bytes) {
+    if (!s || !ms) return fail(BOS_ERR_INVALID, "null argument");
+    for (int i = 0; i < 4; ++i) ms[i] = s->marg_ms[i];
+    if (sigma_bytes) *sigma_bytes = s->mf ? bos::dev::mf_selinv_sigma_bytes(s->mf) : 0;
+    return BOS_OK;
+}
+
+int bos_pair_covariances(bos_solver* s, int64_t n_pairs, const int32_t* node_a, const int32_t* node_b, double* cross,
+                         double* projected, double* cov_a, double* cov_b, int32_t* solver_info) {
+    const char* name = "bos_pair_covariances";
+    int rc;
+    if (!s) return fail(BOS_ERR_INVALID, "null handle");
+    if ((rc = require_one_gpu(s, name, true, " (a rank holds part of the factor)"))) return rc;
+    if (n_pairs < 0 || (n_pairs > 0 && (!node_a || !node_b))) return fail(BOS_ERR_INVALID, std::string(name) + ": bad argument");
+    if (n_pairs == 0) return BOS_OK;
+    if (!bos::pair_ids_valid(s->NP, s->NL, n_pairs, node_a, node_b))
+        return fail(BOS_ERR_INVALID, std::string(name) + ": a node id outside [0, NP + NL), or a mixed pair not written (pose, landmark)");
+    double* const outs[4] = {cross, projected, cov_a, cov_b};
+    bool want[4];
+    for (int i = 0; i < 4; ++i) want[i] = outs[i] != nullptr;
+    HIP_TRY(hipSetDevice(s->device));
+    if (solver_info) *solver_info = 0;
+    for (double& m : s->pair_ms) m = 0.0;
+    if (s->plan.n == 0) {   // the fixed pose alone
+        for (int i = 0; i < 4; ++i)
+            if (want[i]) std::fill(outs[i], outs[i] + 9 * n_pairs, 0.0);
+        return BOS_OK;
+    }
+    typedef std::chrono::steady_clock Clock;
+    auto ms_since = [](Clock::time_point t0) { return std::chrono::duration<double, std::milli>(Clock::now() - t0).count(); };
+    auto t_prep = Clock::now();
+    if (!s->pair_paths_built) {
+        std::string err;
+        if (!bos::pair_paths_build(s->plan, s->pair_paths, err)) return fail(BOS_ERR_UNSUPPORTED, err);
+        if (s->pair_paths.max_m > bos::dev::kPairMaxM)
+            return fail(BOS_ERR_UNSUPPORTED, std::string(name) + ": a front exceeds the path solve's LDS");
+        s->pair_paths_built = true;
+    }
+    if (!s->pair) s->pair = bos::dev::pair_cov_create();
+    s->pair_ms[0] += ms_since(t_prep);
+    // the factorization's word, read and cleared before anything reads the panels
+    int32_t info = 0;
+    if ((rc = enqueue_factorization(s, &info))) return rc;
+    s->pair_ms[1] = elapsed(s->ev[0], s->ev[1]);
+    s->pair_ms[2] = elapsed(s->ev[1], s->ev[2]);
+    if (info & bos::dev::kMfStall)
+        return fail(BOS_ERR_SOLVER, "sparse factorization aborted: a dataflow dependency wait timed out");
+    const bos::dev::MfView view = bos::dev::mf_view(s->mf);
+    const int64_t max_nodes = s->pair_batch_nodes > 0 ? std::max<int64_t>(s->pair_batch_nodes, 2) : INT32_MAX;
+    std::vector<int32_t> slot_of((size_t)s->NP + s->NL, -1);
+    bos::PairBatchHost B;
+    for (int64_t q0 = 0; q0 < n_pairs; q0 += B.nq) {
+        t_prep = Clock::now();
+        bos::pair_batch_build(s->plan, s->pair_paths, n_pairs, node_a, node_b, q0, max_nodes,
+                              bos::dev::kPairYBudgetBytes / (int64_t)sizeof(double), bos::dev::kPairMaxQueries, slot_of, B);
+        bos::dev::PairCovBatch b;
+        b.n_nodes = (int32_t)B.n_node.size(); b.n_queries = B.nq; b.y_count = B.y_count;
+        b.y_off = B.y_off.data(); b.n_sn = B.n_sn.data(); b.n_loc = B.n_loc.data(); b.n_d = B.n_d.data(); b.n_len = B.n_len.data();
+        b.q_a = node_a + q0; b.q_b = node_b + q0; b.q_slot_a = B.q_slot_a.data(); b.q_slot_b = B.q_slot_b.data();
+        b.q_off_a = B.q_off_a.data(); b.q_off_b = B.q_off_b.data(); b.q_c = B.q_c.data();
+        std::string err;
+        int prc = bos::dev::pair_cov_upload(s->pair, b, want, err);
+        if (prc) return fail(prc == -1 ? BOS_ERR_UNSUPPORTED : BOS_ERR_DEVICE, err);
+        s->pair_ms[0] += ms_since(t_prep);
+        bos::dev::PairCovOut res;
+        HIP_TRY(hipEventRecord(s->ev[3], s->stream));
+        prc = bos::dev::pair_cov_enqueue(s->pair, view, s->pair_paths.max_m, s->NP, s->d_pose, s->d_lm, s->stream, s->ev[4], &res, err);
+        hipError_t e = hipEventRecord(s->ev[5], s->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
+        HIP_TRY(e);
+        if (prc) return fail(prc == -1 ? BOS_ERR_UNSUPPORTED : BOS_ERR_DEVICE, err);
+        s->pair_ms[3] += elapsed(s->ev[3], s->ev[4]);
+        s->pair_ms[4] += elapsed(s->ev[4], s->ev[5]);
+        const auto t_dl = Clock::now();
+        const double* dev[4] = {res.cross, res.projected, res.cov_a, res.cov_b};
+        for (int i = 0; i < 4; ++i)
+            if (want[i]) HIP_TRY(hipMemcpy(outs[i] + 9 * q0, dev[i], 9 * (size_t)B.nq * sizeof(double), hipMemcpyDeviceToHost));
+        s->pair_ms[5] += ms_since(t_dl);
+    }
+    if (solver_info) *solver_info = info;
+    return BOS_OK;
+}
+
+int bos_pair_covariances_timing(const bos_solver* s, double ms[6], int64_t* bytes) {
+    if (!s || !ms) return fail(BOS_ERR_INVALID, "null argument");
+    for (int i = 0; i < 6; ++i) ms[i] = s->pair_ms[i];
+    if (bytes) *bytes = bos::dev::pair_cov_bytes(s->pair);
+    return BOS_OK;
+}
+
+int bos_debug_set_pair_batch(bos_solver* s, int64_t max_distinct_nodes) {
+    if (!s || max_distinct_nodes < 0) return fail(BOS_ERR_INVALID, "bad argument");
+    s->pair_batch_nodes = max_distinct_nodes;
+    return BOS_OK;
+}
+
+}  // extern "C"

@@ -391,7 +391,7 @@ void owned_entries(const Plan& P, const std::vector<char>& lane_node, std::vecto
 // fp32 build's factored blocks directly (mf_set_fold_source) and the fp64 copy can skip the region.
 bool mf_fold_reads_fp32(const Plan& P);
 
-// Segments of exchange 1 for rank `rank` (hip/solver_capi.hip): pack = this rank's roots' U / u into
+// Segments of exchange 1 for rank `rank` (hip/solver_create.hip setup_shard): pack = this rank's roots' U / u into
 // its send buffer, unpack = every other rank's roots from the receive buffer (kinds: 0 U, 1 u, 2 send,
 // 3 receive; offsets in doubles).
 struct ExchangeSeg {

@@ -214,7 +214,7 @@ def test_varied_information_steps(varied_world):
 
 def test_information_stride_0_equals_stride_6():
     """A uniform-Omega world (one information row on the device, om_stride 0) and the same world plus
-    one self-loop (p, p) with another Omega (solver_capi.hip then keeps a row per edge, om_stride 6).
+    one self-loop (p, p) with another Omega (solver_create.hip then keeps a row per edge, om_stride 6).
     A self-loop has a zero Jacobian and is kept aside of the lanes, and p, one end of a loop closure, is
     off the odometry-chain shortcut in both worlds, so the lane layout is the same: H and b must agree
     bit for bit, and chi^2 differ by the self-loop's e^T Omega e."""
