@@ -341,6 +341,49 @@ int bos_edge_covariances(struct bos_solver* s, double* bearing_cross, double* od
  * the handle stays usable. */
 int bos_pair_covariances(struct bos_solver* s, int64_t n_pairs, const int32_t* node_a, const int32_t* node_b, double* cross,
                          double* projected, double* cov_a, double* cov_b, int32_t* solver_info);
+/* Node covariances of the current estimate: the covariance of each of n_nodes query nodes against every
+ * node, the block column Sigma(:, a) = H_nf^-1 E_a (which old poses could close a loop with the current
+ * one, which landmarks a new bearing could belong to). Node ids as for bos_pair_covariances: pose stix u is
+ * u, landmark stix l is NP + l; an id outside [0, NP + NL) gives BOS_ERR_INVALID and touches nothing.
+ * n_nodes == 0 returns BOS_OK and touches nothing. Outputs are host pointers, row-major; any may be NULL:
+ * it is neither computed nor downloaded. With i the query index, a = nodes[i], d_a = 3 or 2, each block
+ * fills the first rows * cols entries of its slot, the rest of the slot is exactly 0:
+ *   cross_pose          [n_nodes][NP][9]  Sigma(a, pose u), d_a x 3: rows a's dofs, columns the target's
+ *   cross_landmark      [n_nodes][NL][6]  Sigma(a, landmark l), d_a x 2
+ *   projected_pose      [n_nodes][NP][9]  a pose: the 3 x 3 J Sigma_joint J^T of the odometry prediction
+ *                                         a -> u; a landmark: entry 0 is the variance of the predicted
+ *                                         bearing of landmark a from pose u
+ *   projected_landmark  [n_nodes][NL][4]  a pose: entry 0 is the variance of the predicted bearing of
+ *                                         landmark l from pose a; a landmark: the 2 x 2 covariance of
+ *                                         l_a - l_l
+ *   pose_cov, landmark_cov                as in bos_marginals, bit for bit what it returns at this state
+ * With H_nf = L L^T the column is L^-T (L^-1 E_a): the root-path solve of bos_pair_covariances for the one
+ * node, then one backward substitution over every front of the assembly tree with d_a right-hand sides,
+ * which reads L once; per query node one launch per tree level and front class, then one thread per target
+ * node. The cross block of Sigma_joint comes from the column (transposed for a landmark query against a
+ * pose), both diagonal blocks from the selected inverse of bos_marginals: a call that asks for a projected
+ * output or for pose_cov / landmark_cov runs that pass on the same factorization, a call that asks for cross
+ * blocks only does not. The Jacobians, the state they are evaluated at (fp64 master state, fp64 cos / sin
+ * on every handle) and the projection's arithmetic are those of bos_edge_covariances / bos_pair_covariances.
+ * H_nf, the damping, the kernel threshold, the state handling, the synchronous behaviour, *solver_info,
+ * the clearing of the pivot word, the "counts as a bos_linearize" rule and bos_get_last_dx afterwards are
+ * exactly those of bos_marginals.
+ * Exact rules: with a the fixed pose every cross block is exactly zero (the projections then use the
+ * target's columns only); the block of the fixed pose as target is exactly zero for every a (its
+ * projection uses a's columns only); the own block (u == a) is evaluated like every other one: it is not
+ * promised bit-symmetric, nor bit-equal to bos_marginals, but the projected entry for u == a uses the
+ * marginals' S_aa for all four blocks (the self-loop rule of bos_edge_covariances), so the
+ * landmark-landmark entry is exactly 0; two calls give identical bits; a query's bits do not depend on
+ * the other nodes of the call, and a repeated id returns identical bits.
+ * The buffers (X, one node's output blocks, the index arrays) are allocated at the first call; a handle
+ * that never calls pays nothing.
+ * BOS_ERR_SOLVER on a stalled factorization; BOS_ERR_UNSUPPORTED on BOS_SOLVER_DENSE_CHOL /
+ * BOS_SOLVER_ROCSOLVER_RF handles, on sharded handles, when a front exceeds the path solve's LDS and when a
+ * node's dofs straddle two supernodes (the limits of bos_pair_covariances); BOS_ERR_DEVICE (with the byte
+ * count in bos_last_error) when the feature's buffers cannot be allocated: the handle stays usable. */
+int bos_node_covariances(struct bos_solver* s, int32_t n_nodes, const int32_t* nodes, double* cross_pose,
+                         double* cross_landmark, double* projected_pose, double* projected_landmark, double* pose_cov,
+                         double* landmark_cov, int32_t* solver_info);
 /*
  * Levenberg-Marquardt with on-device step control (DESIGN.md §4 "Levenberg-Marquardt"). The objective is
  *   F(x) = sum over all edges of h(rho), rho = e^T Omega e, h(rho) = rho for rho <= kt and

@@ -124,6 +124,17 @@ int bos_plan_mf_pair_covariances(const bos_problem* problem, const bos_options* 
                                  const int32_t* node_a, const int32_t* node_b, double* cross, double* projected, double* cov_a,
                                  double* cov_b);
 
+/* Test hook: what bos_node_covariances computes, in its literal host form over the host factorization of
+ * H_nf (vals as for bos_plan_mf_marginals): per query node the root-path solve of
+ * bos_plan_mf_pair_covariances, its rows scattered into the zeroed X, the backward substitution over every
+ * front (levels from the root's down, then the folded landmarks; a pivot's sum from the front's last row
+ * up), the host selected inverse for the diagonal blocks, and the gather and projection by the code the
+ * device kernel runs (csrc/host/node_cov.hpp, csrc/host/edge_cov.hpp), J evaluated at the problem's state.
+ * Ids, outputs and rules as for bos_node_covariances; any output may be NULL. No device is used. */
+int bos_plan_mf_node_covariances(const bos_problem* problem, const bos_options* options, const double* vals, int32_t n_nodes,
+                                 const int32_t* nodes, double* cross_pose, double* cross_landmark, double* projected_pose,
+                                 double* projected_landmark, double* pose_cov, double* landmark_cov);
+
 /* The root paths of node pairs, from the plan alone (no values, no device): out[5 * n_pairs] = per pair
  * the supernode of a, the supernode of b (-1: the fixed pose), the lowest common ancestor of the two (-1:
  * none, the nodes hang under two roots; -2: the pair involves the fixed pose), the dofs c the two paths
@@ -211,6 +222,13 @@ int bos_edge_covariances_timing(const struct bos_solver* s, double ms[5], int64_
  * events, summed over the call's batches) and download of the outputs (host clock); *bytes (may be NULL)
  * = bytes of the feature's device buffers (0 before the first call). */
 int bos_pair_covariances_timing(const struct bos_solver* s, double ms[6], int64_t* bytes);
+/* Measurement helper (tools/node_cov_time.py): the last bos_node_covariances call's split, ms[7] = host
+ * preparation and upload (host clock; the plan data and the arena at the first call), J+H build,
+ * factorization, selected inverse (0 when the call did not run it), column solve (path solve, scatter and
+ * backward sweep), gather + projection (HIP events, the last two summed over the call's nodes) and download
+ * of the outputs (host clock); *bytes (may be NULL) = bytes of the feature's device buffers (0 before the
+ * first call). */
+int bos_node_covariances_timing(const struct bos_solver* s, double ms[7], int64_t* bytes);
 /* Test knob: bos_pair_covariances closes a batch at max_distinct_nodes distinct nodes (at least one pair
  * per batch) instead of at its byte budget alone; 0 restores the budget. */
 int bos_debug_set_pair_batch(struct bos_solver* s, int64_t max_distinct_nodes);

@@ -61,6 +61,7 @@ EXPORTED_SYMBOLS = [
     "bos_edge_covariances", "bos_plan_mf_edge_covariances", "bos_edge_covariances_timing",
     "bos_pair_covariances", "bos_plan_mf_pair_covariances", "bos_plan_pair_paths", "bos_pair_covariances_timing",
     "bos_debug_set_pair_batch",
+    "bos_node_covariances", "bos_plan_mf_node_covariances", "bos_node_covariances_timing",
 ]
 
 # bos_lm_result.reason
@@ -222,6 +223,10 @@ def lib():
                                                 _ip, _ip, _ip]),
         "bos_pair_covariances_timing": (ctypes.c_int, [vp, _dp, ctypes.POINTER(ctypes.c_int64)]),
         "bos_debug_set_pair_batch": (ctypes.c_int, [vp, ctypes.c_int64]),
+        "bos_node_covariances": (ctypes.c_int, [vp, ctypes.c_int32, _ip, _dp, _dp, _dp, _dp, _dp, _dp, _ip]),
+        "bos_plan_mf_node_covariances": (ctypes.c_int, [ctypes.POINTER(bos_problem), ctypes.POINTER(bos_options), _dp,
+                                                         ctypes.c_int32, _ip, _dp, _dp, _dp, _dp, _dp, _dp]),
+        "bos_node_covariances_timing": (ctypes.c_int, [vp, _dp, ctypes.POINTER(ctypes.c_int64)]),
         "bos_lm_default_options": (None, [ctypes.POINTER(bos_lm_options)]),
         "bos_cost": (ctypes.c_int, [vp, _dp, _dp, _ip]),
         "bos_optimize": (ctypes.c_int, [vp, ctypes.POINTER(bos_lm_options), ctypes.POINTER(bos_lm_result),
@@ -567,6 +572,38 @@ def plan_mf_pair_covariances(P: Problem, vals, node_a, node_b, solver: int = BOS
                                               _ptr(a, ctypes.c_int32), _ptr(b, ctypes.c_int32),
                                               *[_ptr(out[k], ctypes.c_double) for k in _PAIR_COV_ORDER]),
            "plan_mf_pair_covariances")
+    return out
+
+
+_NODE_COV_ORDER = ("cross_pose", "cross_landmark", "projected_pose", "projected_landmark", "pose_cov", "landmark_cov")
+
+
+def _node_cov_arrays(P: Problem, nodes, cross: bool, projected: bool, marginals: bool):
+    """(nodes as an int32 array, the output dict of a node-covariance call): cross_pose [n, NP, 9],
+    cross_landmark [n, NL, 6], projected_pose [n, NP, 9], projected_landmark [n, NL, 4], pose_cov [NP, 3, 3],
+    landmark_cov [NL, 2, 2]; None where not asked for."""
+    a = np.ascontiguousarray(nodes, dtype=np.int32).ravel()
+    n = len(a)
+    return a, {"cross_pose": np.zeros((n, P.NP, 9)) if cross else None,
+               "cross_landmark": np.zeros((n, P.NL, 6)) if cross else None,
+               "projected_pose": np.zeros((n, P.NP, 9)) if projected else None,
+               "projected_landmark": np.zeros((n, P.NL, 4)) if projected else None,
+               "pose_cov": np.zeros((P.NP, 3, 3)) if marginals else None,
+               "landmark_cov": np.zeros((P.NL, 2, 2)) if marginals else None}
+
+
+def plan_mf_node_covariances(P: Problem, vals, nodes, solver: int = BOS_SOLVER_SCHUR, schur_leaf: int = 0) -> dict:
+    """Host form of Solver.node_covariances() (test hook, bos_plan_mf_node_covariances): per query node
+    the root-path solve, the backward sweep over the host factorization of the H_nf whose stored entries
+    are vals, and the gather and projection at P's state. Returns the dict of arrays, every output asked
+    for (no solver_info)."""
+    cs = P.c_struct()
+    v = np.ascontiguousarray(vals, dtype=np.float64)
+    a, out = _node_cov_arrays(P, nodes, True, True, True)
+    opt = options(solver, schur_leaf=schur_leaf)
+    _check(lib().bos_plan_mf_node_covariances(ctypes.byref(cs), ctypes.byref(opt), _ptr(v, ctypes.c_double), len(a),
+                                              _ptr(a, ctypes.c_int32), *[_ptr(out[k], ctypes.c_double) for k in _NODE_COV_ORDER]),
+           "plan_mf_node_covariances")
     return out
 
 
@@ -1018,6 +1055,31 @@ class Solver:
                "bos_pair_covariances_timing")
         return {"prepare_ms": ms[0], "jh_ms": ms[1], "factor_ms": ms[2], "path_ms": ms[3], "product_ms": ms[4],
                 "download_ms": ms[5], "pair_bytes": nb.value}
+
+    def node_covariances(self, nodes, cross: bool = True, projected: bool = True, marginals: bool = False) -> dict:
+        """One node's covariance against every node, for each node of `nodes`, at the current estimate
+        (bos_node_covariances). Node ids: pose stix u is u, landmark stix l is NP + l. Returns a dict with
+        cross_pose [n, NP, 9] and cross_landmark [n, NL, 6] (cross: Sigma(a, u), rows a's dofs, row-major in
+        the first rows * cols entries of a slot), projected_pose [n, NP, 9] and projected_landmark [n, NL, 4]
+        (projected), pose_cov [NP, 3, 3] and landmark_cov [NL, 2, 2] (marginals), and solver_info; outputs not
+        asked for are None."""
+        a, out = _node_cov_arrays(self.P, nodes, cross, projected, marginals)
+        info = ctypes.c_int32(0)
+        _check(lib().bos_node_covariances(self._h, len(a), _ptr(a, ctypes.c_int32),
+                                          *[_ptr(out[k], ctypes.c_double) for k in _NODE_COV_ORDER], ctypes.byref(info)),
+               "bos_node_covariances")
+        out["solver_info"] = info.value
+        return out
+
+    def node_covariances_timing(self) -> dict:
+        """The last node_covariances() call's split in ms and the feature's device bytes
+        (bos_node_covariances_timing)."""
+        ms = np.zeros(7)
+        nb = ctypes.c_int64(0)
+        _check(lib().bos_node_covariances_timing(self._h, _ptr(ms, ctypes.c_double), ctypes.byref(nb)),
+               "bos_node_covariances_timing")
+        return {"prepare_ms": ms[0], "jh_ms": ms[1], "factor_ms": ms[2], "selinv_ms": ms[3], "column_ms": ms[4],
+                "gather_ms": ms[5], "download_ms": ms[6], "node_bytes": nb.value}
 
     def debug_set_pair_batch(self, max_distinct_nodes: int):
         """Test knob (bos_debug_set_pair_batch): pair_covariances() closes a batch at this many distinct

@@ -302,19 +302,22 @@ int pair_cov_upload(PairCov* p, const PairCovBatch& b, const bool want[4], std::
     return 0;
 }
 
+hipError_t pair_path_enqueue(const MfView& v, int max_m, int n_nodes, const int32_t* n_sn, const int32_t* n_loc, const int32_t* n_d,
+                             const int64_t* y_off, double* Y, hipStream_t s) {
+    if (n_nodes <= 0) return hipSuccess;
+    PathArgs a;
+    a.k = v.k; a.r = v.r; a.parent = v.parent; a.rmap = v.rmap; a.L_off = v.L_off; a.rmap_off = v.rmap_off; a.L = v.L;
+    a.n_sn = n_sn; a.n_loc = n_loc; a.n_d = n_d; a.y_off = y_off; a.Y = Y;
+    a.buf = max_m * 3;
+    pair_path_kernel<<<n_nodes, kWave, 2 * (size_t)a.buf * sizeof(double), s>>>(a);
+    return hipGetLastError();
+}
+
 int pair_cov_enqueue(PairCov* p, const MfView& v, int max_m, int NP, const double* pose, const double* lm, hipStream_t s,
                      hipEvent_t after_solve, PairCovOut* out, std::string& err) {
     if (!p->arena) { err = "bos_pair_covariances: no batch uploaded"; return -1; }
     if (max_m > kPairMaxM) { err = "bos_pair_covariances: a front of " + std::to_string(max_m) + " rows exceeds the path solve's LDS"; return -1; }
-    hipError_t e = hipSuccess;
-    if (p->n_nodes > 0) {
-        PathArgs a;
-        a.k = v.k; a.r = v.r; a.parent = v.parent; a.rmap = v.rmap; a.L_off = v.L_off; a.rmap_off = v.rmap_off; a.L = v.L;
-        a.n_sn = p->n_sn; a.n_loc = p->n_loc; a.n_d = p->n_d; a.y_off = p->y_off; a.Y = p->Y;
-        a.buf = max_m * 3;
-        pair_path_kernel<<<p->n_nodes, kWave, 2 * (size_t)a.buf * sizeof(double), s>>>(a);
-        e = hipGetLastError();
-    }
+    hipError_t e = pair_path_enqueue(v, max_m, p->n_nodes, p->n_sn, p->n_loc, p->n_d, p->y_off, p->Y, s);
     if (e == hipSuccess && after_solve) e = hipEventRecord(after_solve, s);
     ProdArgs g;
     g.n_diag = p->diag ? p->n_nodes : 0;

@@ -46,6 +46,11 @@ int64_t pair_cov_bytes(const PairCov* p);
 // is idle between batches). want[4]: cross, projected, cov_a, cov_b. 0; -2 with err (the byte count) when
 // the allocation fails: the arena is then empty, nothing else is touched.
 int pair_cov_upload(PairCov* p, const PairCovBatch& b, const bool want[4], std::string& err);
+// The path solve alone (bos_node_covariances' forward half): one wavefront per node i < n_nodes, its start
+// supernode n_sn[i], first dof inside it n_loc[i] and dofs n_d[i], its slice at Y + y_off[i]; device arrays.
+// max_m <= kPairMaxM is the caller's to check.
+hipError_t pair_path_enqueue(const MfView& v, int max_m, int n_nodes, const int32_t* n_sn, const int32_t* n_loc, const int32_t* n_d,
+                             const int64_t* y_off, double* Y, hipStream_t s);
 // Enqueues the three kernels of the uploaded batch on s; after_solve (may be null) is recorded behind the
 // path solve. v: the factor's view; max_m: PairPaths::max_m (<= kPairMaxM); pose / lm: the fp64 master state.
 int pair_cov_enqueue(PairCov* p, const MfView& v, int max_m, int NP, const double* pose, const double* lm, hipStream_t s,

@@ -1,5 +1,5 @@
-// Covariances from the multifrontal factor on the C ABI handle (solver_handle.hpp): marginals, edge and
-// pair covariances (hip/selinv.hpp, hip/pair_cov.hpp).
+// Covariances from the multifrontal factor on the C ABI handle (solver_handle.hpp): marginals, edge, pair
+// and node covariances (hip/selinv.hpp, hip/pair_cov.hpp, hip/node_cov.hpp).
 #include <algorithm>
 #include <chrono>
 
@@ -53,6 +53,17 @@ int enqueue_factorization(bos_solver* s, int32_t* info_now) {
     s->have_dx = false;   // d_rhs now holds L^-1 b of this factorization
     HIP_TRY(hipEventRecord(s->ev[2], s->stream));
     if (info_now) HIP_TRY(take_factor_info(s, info_now));
+    return BOS_OK;
+}
+
+// The static path data of the pair and node covariances, at the first call of either
+int pair_paths_setup(bos_solver* s, const char* name) {
+    if (s->pair_paths_built) return BOS_OK;
+    std::string err;
+    if (!bos::pair_paths_build(s->plan, s->pair_paths, err)) return fail(BOS_ERR_UNSUPPORTED, err);
+    if (s->pair_paths.max_m > bos::dev::kPairMaxM)
+        return fail(BOS_ERR_UNSUPPORTED, std::string(name) + ": a front exceeds the path solve's LDS");
+    s->pair_paths_built = true;
     return BOS_OK;
 }
 
@@ -183,13 +194,7 @@ int bos_pair_covariances(bos_solver* s, int64_t n_pairs, const int32_t* node_a, 
     typedef std::chrono::steady_clock Clock;
     auto ms_since = [](Clock::time_point t0) { return std::chrono::duration<double, std::milli>(Clock::now() - t0).count(); };
     auto t_prep = Clock::now();
-    if (!s->pair_paths_built) {
-        std::string err;
-        if (!bos::pair_paths_build(s->plan, s->pair_paths, err)) return fail(BOS_ERR_UNSUPPORTED, err);
-        if (s->pair_paths.max_m > bos::dev::kPairMaxM)
-            return fail(BOS_ERR_UNSUPPORTED, std::string(name) + ": a front exceeds the path solve's LDS");
-        s->pair_paths_built = true;
-    }
+    if ((rc = pair_paths_setup(s, name))) return rc;
     if (!s->pair) s->pair = bos::dev::pair_cov_create();
     s->pair_ms[0] += ms_since(t_prep);
     // the factorization's word, read and cleared before anything reads the panels
@@ -239,6 +244,94 @@ int bos_pair_covariances_timing(const bos_solver* s, double ms[6], int64_t* byte
     if (!s || !ms) return fail(BOS_ERR_INVALID, "null argument");
     for (int i = 0; i < 6; ++i) ms[i] = s->pair_ms[i];
     if (bytes) *bytes = bos::dev::pair_cov_bytes(s->pair);
+    return BOS_OK;
+}
+
+int bos_node_covariances(bos_solver* s, int32_t n_nodes, const int32_t* nodes, double* cross_pose, double* cross_landmark,
+                         double* projected_pose, double* projected_landmark, double* pose_cov, double* landmark_cov,
+                         int32_t* solver_info) {
+    const char* name = "bos_node_covariances";
+    int rc;
+    if (!s) return fail(BOS_ERR_INVALID, "null handle");
+    if ((rc = require_one_gpu(s, name, true, " (a rank holds part of the factor)"))) return rc;
+    if (n_nodes < 0 || (n_nodes > 0 && !nodes)) return fail(BOS_ERR_INVALID, std::string(name) + ": bad argument");
+    if (n_nodes == 0) return BOS_OK;
+    if (!bos::node_ids_valid(s->NP, s->NL, n_nodes, nodes))
+        return fail(BOS_ERR_INVALID, std::string(name) + ": a node id outside [0, NP + NL)");
+    const size_t np9 = 9 * (size_t)s->NP, nl4 = 4 * (size_t)s->NL;
+    const size_t count[4] = {np9, 6 * (size_t)s->NL, np9, nl4};
+    double* const outs[4] = {cross_pose, cross_landmark, projected_pose, projected_landmark};
+    bool want[4], any_node = false;
+    for (int i = 0; i < 4; ++i) any_node |= want[i] = outs[i] != nullptr && count[i] > 0;
+    const bool projected = want[2] || want[3], need_sig = projected || pose_cov || (landmark_cov && nl4);
+    HIP_TRY(hipSetDevice(s->device));
+    if (solver_info) *solver_info = 0;
+    for (double& m : s->node_ms) m = 0.0;
+    if (s->plan.n == 0) {   // the fixed pose alone
+        for (int i = 0; i < 4; ++i)
+            if (want[i]) std::fill(outs[i], outs[i] + (size_t)n_nodes * count[i], 0.0);
+        if (pose_cov) std::fill(pose_cov, pose_cov + np9, 0.0);
+        return BOS_OK;
+    }
+    typedef std::chrono::steady_clock Clock;
+    auto ms_since = [](Clock::time_point t0) { return std::chrono::duration<double, std::milli>(Clock::now() - t0).count(); };
+    const auto t_prep = Clock::now();
+    if (any_node && !bos::dev::node_cov_built(s->node)) {
+        std::string err;
+        if ((rc = pair_paths_setup(s, name))) return rc;
+        if (!bos::node_cov_plan_build(s->plan, s->pair_paths, s->node_plan, err)) return fail(BOS_ERR_UNSUPPORTED, err);
+        if (!s->node) s->node = bos::dev::node_cov_create();
+        if (bos::dev::node_cov_build(s->node, s->plan, s->pair_paths, s->node_plan, err)) return fail(BOS_ERR_DEVICE, err);
+    }
+    s->node_ms[0] = ms_since(t_prep);
+    // the factorization's word, read and cleared before anything reads the panels
+    int32_t info = 0;
+    if ((rc = enqueue_factorization(s, &info))) return rc;
+    s->node_ms[1] = elapsed(s->ev[0], s->ev[1]);
+    s->node_ms[2] = elapsed(s->ev[1], s->ev[2]);
+    if (info & bos::dev::kMfStall)
+        return fail(BOS_ERR_SOLVER, "sparse factorization aborted: a dataflow dependency wait timed out");
+    const double* sig = nullptr;
+    if (need_sig) {   // the marginals' own pass on this factorization
+        std::string err;
+        const int src = bos::dev::mf_selected_inverse(s->mf, s->plan, &sig, s->stream, err);
+        hipError_t e = hipEventRecord(s->ev[3], s->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
+        HIP_TRY(e);
+        if (src) return fail(src == -1 ? BOS_ERR_UNSUPPORTED : BOS_ERR_DEVICE, err);
+        s->node_ms[3] = elapsed(s->ev[2], s->ev[3]);
+    }
+    const bos::dev::MfView view = bos::dev::mf_view(s->mf);
+    for (int32_t q = 0; q < n_nodes && any_node; ++q) {
+        std::string err;
+        bos::dev::NodeCovDev res;
+        HIP_TRY(hipEventRecord(s->ev[4], s->stream));
+        const int prc = bos::dev::node_cov_enqueue(s->node, view, nodes[q], nodes[q] == s->plan.fixed, want, projected ? sig : nullptr,
+                                                   s->d_pose, s->d_lm, s->stream, s->ev[5], &res, err);
+        hipError_t e = hipEventRecord(s->ev[6], s->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
+        HIP_TRY(e);
+        if (prc) return fail(prc == -1 ? BOS_ERR_UNSUPPORTED : BOS_ERR_DEVICE, err);
+        s->node_ms[4] += elapsed(s->ev[4], s->ev[5]);
+        s->node_ms[5] += elapsed(s->ev[5], s->ev[6]);
+        const auto t_dl = Clock::now();
+        const double* dev[4] = {res.cross_pose, res.cross_landmark, res.projected_pose, res.projected_landmark};
+        for (int i = 0; i < 4; ++i)
+            if (want[i]) HIP_TRY(hipMemcpy(outs[i] + (size_t)q * count[i], dev[i], count[i] * sizeof(double), hipMemcpyDeviceToHost));
+        s->node_ms[6] += ms_since(t_dl);
+    }
+    const auto t_dl = Clock::now();
+    if (pose_cov) HIP_TRY(hipMemcpy(pose_cov, sig, np9 * sizeof(double), hipMemcpyDeviceToHost));
+    if (landmark_cov && nl4) HIP_TRY(hipMemcpy(landmark_cov, sig + np9, nl4 * sizeof(double), hipMemcpyDeviceToHost));
+    s->node_ms[6] += ms_since(t_dl);
+    if (solver_info) *solver_info = info;
+    return BOS_OK;
+}
+
+int bos_node_covariances_timing(const bos_solver* s, double ms[7], int64_t* bytes) {
+    if (!s || !ms) return fail(BOS_ERR_INVALID, "null argument");
+    for (int i = 0; i < 7; ++i) ms[i] = s->node_ms[i];
+    if (bytes) *bytes = bos::dev::node_cov_bytes(s->node);
     return BOS_OK;
 }
 

@@ -1,7 +1,7 @@
 // The C ABI handle (include/bos.h) and what its implementation files share: solver_create.hip (plan,
 // uploads, bos_create / bos_destroy), solver_step.hip (the GN step, its graphs and the step's entry
-// points), solver_shard.hip (the multi-rank phases and exchanges), solver_cov.hip (marginals, edge and
-// pair covariances) and solver_lm.hip (bos_cost / bos_optimize). The handle owns every device buffer
+// points), solver_shard.hip (the multi-rank phases and exchanges), solver_cov.hip (marginals, edge,
+// pair and node covariances) and solver_lm.hip (bos_cost / bos_optimize). The handle owns every device buffer
 // (mem), the static plan (host/plan.hpp), the rocSOLVER refactorization state and the RCCL communicator.
 #pragma once
 
@@ -23,6 +23,7 @@
 #include "kernels.hpp"
 #include "lm.hpp"
 #include "multifrontal.hpp"
+#include "node_cov.hpp"
 #include "pair_cov.hpp"
 #include "selinv.hpp"
 
@@ -181,6 +182,12 @@ struct bos_solver {
     bos::dev::PairCov* pair = nullptr;
     double pair_ms[6] = {};
     int64_t pair_batch_nodes = 0;
+    // bos_node_covariances (hip/node_cov.hpp): the sweep's order and the device arena, both built at the
+    // first call (with pair_paths); the last call's split (host preparation and upload, J+H, factorization,
+    // selected inverse, column solve, gather + projection, download)
+    bos::NodeCovPlan node_plan;
+    bos::dev::NodeCov* node = nullptr;
+    double node_ms[7] = {};
     // ---- bos_cost / bos_optimize (hip/lm.hpp). The fp64 originals of what the cost pass reads and the
     // J+H keeps only in T: odometry z / information (upper triangle) and the bearing weights (has_w)
     std::vector<double> h_oz, h_oom, h_bw;

@@ -11,6 +11,7 @@
 
 #include "../../../include/bos_host.h"
 #include "edge_cov.hpp"
+#include "node_cov.hpp"
 #include "pair_cov.hpp"
 #include "g2o_utils.hpp"
 #include "host_mf.hpp"
@@ -564,6 +565,61 @@ int bos_plan_mf_pair_covariances(const bos_problem* pb, const bos_options* optio
     bos::PairQueryOut o;
     o.cross = cross; o.projected = projected; o.cov_a = cov_a; o.cov_b = cov_b;
     for (int64_t q = 0; q < n_pairs; ++q) bos::pair_cov_query(in, o, q);
+    return BOS_OK;
+}
+
+// Test hook: bos_node_covariances in its literal host form (csrc/host/node_cov.hpp): the host
+// factorization, per query node the root-path solve, the scatter into X and the backward sweep over every
+// front, the host selected inverse for the diagonal blocks, and the per-target gather and projection the
+// device kernel runs, at the problem's state (theta wrapped as bos_create wraps it).
+int bos_plan_mf_node_covariances(const bos_problem* pb, const bos_options* options, const double* vals, int32_t n_nodes,
+                                 const int32_t* nodes, double* cross_pose, double* cross_landmark, double* projected_pose,
+                                 double* projected_landmark, double* pose_cov, double* landmark_cov) {
+    if (!pb || !vals || !pb->pose_xyt || (!pb->landmark_xy && pb->num_landmarks > 0) || n_nodes < 0 || (n_nodes > 0 && !nodes))
+        return hfail(BOS_ERR_INVALID, "bad argument");
+    if (n_nodes == 0) return BOS_OK;
+    if (!bos::node_ids_valid(pb->num_poses, pb->num_landmarks, n_nodes, nodes))
+        return hfail(BOS_ERR_INVALID, "bos_node_covariances: a node id outside [0, NP + NL)");
+    bos::ProblemIndex pi;
+    bos::Plan P;
+    bos::PairPaths pp;
+    const int rc = pair_plan(pb, options, pi, P, pp);
+    if (rc) return rc;
+    bos::NodeCovPlan np;
+    std::string err;
+    if (!bos::node_cov_plan_build(P, pp, np, err)) return hfail(BOS_ERR_UNSUPPORTED, err);
+    const std::vector<double> rhs(P.n, 0.0);
+    bos::HostMf M(P, vals, rhs.data());
+    M.factor([](int) { return true; });
+    const size_t np9 = 9 * (size_t)P.NP, nl4 = 4 * (size_t)P.NL, nl6 = 6 * (size_t)P.NL;
+    std::vector<double> sig(np9 + nl4 + 1);
+    const bool need_sig = projected_pose || projected_landmark || pose_cov || landmark_cov;
+    if (need_sig && !M.selected_inverse(sig.data(), sig.data() + np9))
+        return hfail(BOS_ERR_UNSUPPORTED, "a node's dofs are split between two supernodes");
+    std::vector<double> pose(pb->pose_xyt, pb->pose_xyt + 3 * (size_t)P.NP);
+    for (int i = 0; i < P.NP; ++i) pose[3 * i + 2] = bos::normalized_angle<double>(bos::smallest_angle<double>(pose[3 * i + 2]));
+    std::vector<double> Y(3 * (size_t)np.max_path + 1), X(3 * (size_t)P.n + 1);
+    for (int32_t q = 0; q < n_nodes; ++q) {
+        const int a = nodes[q], d = a < P.NP ? 3 : 2;
+        const bool fixed = a == P.fixed;
+        if (!fixed) {
+            bos::pair_path_solve_host(P.mf, pp, M.L.data(), pp.node_sn[a], pp.node_loc[a], d, Y.data());
+            bos::node_cov_scatter_host(P.mf, pp, P.n, pp.node_sn[a], d, Y.data(), X.data());
+            bos::node_cov_backward_host(P.mf, np, M.L.data(), d, X.data());
+        }
+        bos::NodeCovIn in;
+        in.NP = P.NP; in.NL = P.NL; in.a = a; in.d = d; in.n = P.n;
+        in.pose = pose.data(); in.lm = pb->landmark_xy; in.X = fixed ? nullptr : X.data(); in.node_dof = P.node_dof.data();
+        in.sig = need_sig ? sig.data() : nullptr;
+        bos::NodeCovOut o;
+        o.cross_pose = cross_pose ? cross_pose + q * np9 : nullptr;
+        o.cross_landmark = cross_landmark ? cross_landmark + q * nl6 : nullptr;
+        o.projected_pose = projected_pose ? projected_pose + q * np9 : nullptr;
+        o.projected_landmark = projected_landmark ? projected_landmark + q * nl4 : nullptr;
+        for (int u = 0; u < P.NP + P.NL; ++u) bos::node_cov_target(in, o, u);
+    }
+    if (pose_cov) std::copy(sig.begin(), sig.begin() + np9, pose_cov);
+    if (landmark_cov) std::copy(sig.begin() + np9, sig.begin() + np9 + nl4, landmark_cov);
     return BOS_OK;
 }
 
