@@ -272,7 +272,8 @@ int bos_debug_solver_stamps(struct bos_solver* s, int64_t capacity, uint64_t* st
 
 /* Diagnostics: the kernel route every front of the multifrontal tree takes in this handle's launch
  * sequence. One value per launch site of the factorization (mf_factor_t) and of the backward
- * substitution (mf_solve) in hip/multifrontal.hip; the launch sites themselves note it, with the
+ * substitution (mf_solve) in hip/multifrontal.hip (the kernels they launch are in hip/mf_level.hpp,
+ * mf_blk.hpp, mf_wave.hpp and mf_backward.hpp); the launch sites themselves note it, with the
  * front list they launch, the first time the sequence is enqueued (a replayed graph enqueues it
  * once, at capture). Nothing is launched or changed by the call. */
 enum {

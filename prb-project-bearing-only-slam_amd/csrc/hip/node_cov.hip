@@ -20,6 +20,7 @@
 // node_gather_kernel: one thread per target node (host/node_cov.hpp node_cov_target).
 #include "node_cov.hpp"
 #include "device_mem.hpp"
+#include "wave_util.hpp"
 
 #include <algorithm>
 #include <vector>
@@ -41,13 +42,6 @@ struct SweepArgs {
     double* X;
     int first;   // the launch's fronts: order[first + blockIdx.x]
 };
-
-__device__ __forceinline__ double readlane_d(double x, int l) {
-    const long long b = __double_as_longlong(x);
-    const int lo = __builtin_amdgcn_readlane((int)(b & 0xffffffffll), l);
-    const int hi = __builtin_amdgcn_readlane((int)(b >> 32), l);
-    return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
-}
 
 // The pivots b0 .. b0 + nb - 1 (nb <= 64) of a front, everything below them already subtracted: lane l < nb
 // holds t of pivot b0 + l in acc and leaves with its x. From the last pivot up; lane l's panel entries are

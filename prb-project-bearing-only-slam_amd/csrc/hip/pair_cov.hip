@@ -18,6 +18,7 @@
 // pair_project_kernel: one thread per query (host/pair_cov.hpp pair_cov_query).
 #include "pair_cov.hpp"
 #include "device_mem.hpp"
+#include "wave_util.hpp"
 
 #include <algorithm>
 
@@ -40,13 +41,6 @@ struct PathArgs {
     double* Y;
     int buf;   // doubles of one w buffer
 };
-
-__device__ __forceinline__ double readlane_d(double x, int l) {
-    const long long b = __double_as_longlong(x);
-    const int lo = __builtin_amdgcn_readlane((int)(b & 0xffffffffll), l);
-    const int hi = __builtin_amdgcn_readlane((int)(b >> 32), l);
-    return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
-}
 
 template <int D> __device__ void path_solve(const PathArgs& a, int node, double* wl, double* wn) {
     const int lane = threadIdx.x;

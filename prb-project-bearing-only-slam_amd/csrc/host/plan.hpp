@@ -147,9 +147,9 @@ struct OrderingReport {
 //  - update matrices U are packed lower-triangular column-major (r (r + 1) / 2 values) for all.
 //  - L panels are m x k column-major (entries above the diagonal unused).
 constexpr int kMfWaveMaxM = 64;
-constexpr int kMfFlowMaxM = 48;   // fronts of the dataflow factor launch (hip/multifrontal.hip kFlowMaxM)
+constexpr int kMfFlowMaxM = 48;   // fronts of the dataflow factor launch (hip/mf_wave.hpp kFlowMaxM)
 constexpr int kMfBlkMaxM = 128;   // fronts of 65-128 rows: one workgroup, the front in LDS, blocked on MFMA
-                                  // (hip/multifrontal.hip mf_factor_blk); landmarks fold into them too
+                                  // (hip/mf_blk.hpp mf_factor_blk); landmarks fold into them too
 constexpr int kFoldChunk = 64;   // folded row groups per chunk (one per lane)
 constexpr int kFoldRec = 8;      // ints per folded row group (the 3 rows of one observing pose)
 // fold record word 6: t (row of the landmark's update rows, 6 bits) | r[c] << 6 (6 bits) | the row's

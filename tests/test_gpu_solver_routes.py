@@ -1,8 +1,8 @@
 """The multifrontal solve against an exact answer, kernel route by kernel route.
 
 The solve chooses among a dozen kernel routes by front size, tree level and level population
-(hip/multifrontal.hip mf_factor_t / mf_solve). Each case here is one small world whose plan takes
-known routes (helpers.SOLVER_WORLDS; DESIGN.md §5 has the table); the routes are read from the
+(hip/multifrontal.hip mf_factor_t / mf_solve; the kernels are in hip/mf_*.hpp). Each case here is
+one small world whose plan takes known routes (helpers.SOLVER_WORLDS; DESIGN.md §5 has the table); the routes are read from the
 launch sites' own report (Solver.debug_solver_routes), and test_every_route_is_covered fails when a
 route of the enum is neither taken by a case nor listed, with its reason, in UNREACHED.
 

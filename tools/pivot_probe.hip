@@ -1,4 +1,4 @@
-// The multifrontal front's two-pivot loop (hip/multifrontal.hip factor_front_reg, product form) in
+// The multifrontal front's two-pivot loop (hip/mf_wave.hpp factor_front_reg, product form) in
 // isolation (diagnostic): one wavefront factors an m x m SPD front's first k columns with the rows
 // in registers, s_memtime around every two-pivot step. Variants drop the L-panel stores or the fused
 // forward step, to see what the step's cycles are made of. Prints the median cycles per step.

@@ -1,5 +1,5 @@
 // Accuracy of the f64 reciprocal square root estimate (v_rsq_f64) and of one and two Newton steps
-// (multifrontal.hip rsqrt_nr), against 1 / sqrtl(d) on the host in long double. Diagnostics only.
+// (hip/mf_device.hpp rsqrt_nr), against 1 / sqrtl(d) on the host in long double. Diagnostics only.
 // Build: hipcc --offload-arch=gfx950 -O2 -o tools/rsq_probe tools/rsq_probe.cpp
 #include <hip/hip_runtime.h>
 #include <cmath>
