@@ -384,6 +384,52 @@ int bos_pair_covariances(struct bos_solver* s, int64_t n_pairs, const int32_t* n
 int bos_node_covariances(struct bos_solver* s, int32_t n_nodes, const int32_t* nodes, double* cross_pose,
                          double* cross_landmark, double* projected_pose, double* projected_landmark, double* pose_cov,
                          double* landmark_cov, int32_t* solver_info);
+/* Bearing association at the current estimate: n_bearings new bearings, bearing q measured as z[q] from
+ * pose stix pose[q] with information omega[q] (omega NULL: 1 for every bearing), each gated against every
+ * landmark of the problem on the device. For bearing q, a = pose[q] and landmark stix l:
+ *   e   = bearing_error<double> (csrc/host/bos_math.hpp) = normalized_angle(predicted bearing of l from a - z[q]),
+ *         at the fp64 master state with cos / sin computed in fp64, on every handle, fp32 ones included (as
+ *         bos_cost); z may be any finite value, it is not wrapped first
+ *   var = the variance of the predicted bearing of l from a: exactly the number bos_node_covariances puts in
+ *         projected_landmark[.][l][0] for the query node a, by the same device code and with its fixed-pose
+ *         rule (from the fixed pose it is J_l S_ll J_l^T)
+ *   S   = var + 1.0 / omega[q]
+ *   nis = (e * e) / S, evaluated in this order without FP contraction: a caller reproduces its bits from e
+ *         and S with IEEE arithmetic
+ * Outputs (host pointers; any may be NULL: it is neither computed nor downloaded), k in 1 .. BOS_ASSOC_MAX_K:
+ *   cand_landmark   [n_bearings][k]  landmark stix, -1 where nothing is listed
+ *   cand_nis        [n_bearings][k]  +inf where nothing is listed; bit for bit nis_all[q][cand_landmark[q][j]]
+ *   cand_innovation [n_bearings][k]  e of the listed landmark, 0 where nothing is listed
+ *   cand_var        [n_bearings][k]  S of the listed landmark, 0 where nothing is listed
+ *   n_inside        [n_bearings]     landmarks with nis <= gate: all of them, not min(., k)
+ *   nis_all         [n_bearings][NL] the whole row
+ * The listed candidates are the min(k, n_inside) smallest NIS among the landmarks with nis <= gate, ascending
+ * by (nis, landmark stix): equal NIS go to the lower stix first. A nis that is not finite (a landmark that
+ * sits on the pose) is never listed and never counted; nis_all still holds what was computed. Landmarks the
+ * pose already observes are not excluded: the caller knows its edges. gate may be +inf.
+ * n_bearings == 0 returns BOS_OK and touches nothing; with NL == 0 every count is 0 and every list is
+ * padding. BOS_ERR_INVALID, with nothing touched, for a pose outside [0, NP), a z that is not finite, an
+ * omega that is not finite and positive, a gate that is NaN or <= 0 and k outside 1 .. BOS_ASSOC_MAX_K.
+ * The bearings are grouped by pose. Per distinct pose: the column solve and gather of bos_node_covariances
+ * for projected_landmark alone, read in place on the device; then, per chunk of that pose's bearings (a
+ * chunk's NIS rows stay within 64 MiB), one kernel with a thread per landmark and bearing and two selection
+ * launches (per tile of landmarks and bearing, then per bearing); per chunk k entries and a count per
+ * bearing are downloaded, the rows only for nis_all.
+ * H_nf, the damping, the kernel threshold, the state handling, the synchronous behaviour, *solver_info,
+ * the clearing of the pivot word, the "counts as a bos_linearize" rule and bos_get_last_dx afterwards are
+ * exactly those of bos_marginals.
+ * Exact rules: two calls give identical bits; a bearing's results depend neither on the other bearings of
+ * the call, nor on their order, nor on how the call is split into chunks; a repeated (pose, z, omega)
+ * returns identical bits.
+ * The buffers are allocated at the first call (with those of bos_node_covariances, if it has not run); a
+ * handle that never calls pays nothing.
+ * BOS_ERR_SOLVER, BOS_ERR_UNSUPPORTED and BOS_ERR_DEVICE on exactly the conditions of bos_node_covariances:
+ * the handle stays usable. */
+#define BOS_ASSOC_MAX_K 8
+int bos_associate_bearings(struct bos_solver* s, int32_t n_bearings, const int32_t* pose, const double* z,
+                           const double* omega, double gate, int32_t k, int32_t* cand_landmark, double* cand_nis,
+                           double* cand_innovation, double* cand_var, int32_t* n_inside, double* nis_all,
+                           int32_t* solver_info);
 /*
  * Levenberg-Marquardt with on-device step control (DESIGN.md §4 "Levenberg-Marquardt"). The objective is
  *   F(x) = sum over all edges of h(rho), rho = e^T Omega e, h(rho) = rho for rho <= kt and

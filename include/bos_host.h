@@ -135,6 +135,18 @@ int bos_plan_mf_node_covariances(const bos_problem* problem, const bos_options* 
                                  const int32_t* nodes, double* cross_pose, double* cross_landmark, double* projected_pose,
                                  double* projected_landmark, double* pose_cov, double* landmark_cov);
 
+/* Test hook: what bos_associate_bearings computes, in its literal host form: per distinct pose the column of
+ * bos_plan_mf_node_covariances for projected_landmark, then e, S and nis by the code the device kernels run
+ * (csrc/host/associate.hpp), at the problem's state, and the selection by a plain sort over (nis, stix).
+ * Arguments, outputs and rules as for bos_associate_bearings; any output may be NULL. No device is used. */
+int bos_plan_mf_associate_bearings(const bos_problem* problem, const bos_options* options, const double* vals,
+                                   int32_t n_bearings, const int32_t* pose, const double* z, const double* omega, double gate,
+                                   int32_t k, int32_t* cand_landmark, double* cand_nis, double* cand_innovation,
+                                   double* cand_var, int32_t* n_inside, double* nis_all);
+/* Test constant: the landmarks one workgroup of bos_associate_bearings' first selection stage takes (a
+ * world needs more than that to have a second tile). */
+int32_t bos_associate_tile(void);
+
 /* The root paths of node pairs, from the plan alone (no values, no device): out[5 * n_pairs] = per pair
  * the supernode of a, the supernode of b (-1: the fixed pose), the lowest common ancestor of the two (-1:
  * none, the nodes hang under two roots; -2: the pair involves the fixed pose), the dofs c the two paths
@@ -229,6 +241,16 @@ int bos_pair_covariances_timing(const struct bos_solver* s, double ms[6], int64_
  * of the outputs (host clock); *bytes (may be NULL) = bytes of the feature's device buffers (0 before the
  * first call). */
 int bos_node_covariances_timing(const struct bos_solver* s, double ms[7], int64_t* bytes);
+/* Measurement helper (tools/associate_time.py): the last bos_associate_bearings call's split, ms[8] = host
+ * preparation (host clock; the plan data and the buffers at the first call), J+H build, factorization,
+ * selected inverse, column solve and gather (summed over the call's distinct poses), NIS kernel, selection
+ * (HIP events, the last two summed over the call's chunks) and download of the outputs (host clock); *bytes
+ * (may be NULL) = bytes of the feature's own device buffers (0 before the first call; the column's are
+ * bos_node_covariances_timing's). */
+int bos_associate_bearings_timing(const struct bos_solver* s, double ms[8], int64_t* bytes);
+/* Test knob: bos_associate_bearings closes a chunk at max_bearings bearings of one pose instead of at its
+ * byte budget alone; 0 restores the budget. */
+int bos_debug_set_associate_chunk(struct bos_solver* s, int64_t max_bearings);
 /* Test knob: bos_pair_covariances closes a batch at max_distinct_nodes distinct nodes (at least one pair
  * per batch) instead of at its byte budget alone; 0 restores the budget. */
 int bos_debug_set_pair_batch(struct bos_solver* s, int64_t max_distinct_nodes);

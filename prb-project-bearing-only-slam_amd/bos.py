@@ -62,6 +62,8 @@ EXPORTED_SYMBOLS = [
     "bos_pair_covariances", "bos_plan_mf_pair_covariances", "bos_plan_pair_paths", "bos_pair_covariances_timing",
     "bos_debug_set_pair_batch",
     "bos_node_covariances", "bos_plan_mf_node_covariances", "bos_node_covariances_timing",
+    "bos_associate_bearings", "bos_plan_mf_associate_bearings", "bos_associate_bearings_timing",
+    "bos_debug_set_associate_chunk", "bos_associate_tile",
 ]
 
 # bos_lm_result.reason
@@ -227,6 +229,14 @@ def lib():
         "bos_plan_mf_node_covariances": (ctypes.c_int, [ctypes.POINTER(bos_problem), ctypes.POINTER(bos_options), _dp,
                                                          ctypes.c_int32, _ip, _dp, _dp, _dp, _dp, _dp, _dp]),
         "bos_node_covariances_timing": (ctypes.c_int, [vp, _dp, ctypes.POINTER(ctypes.c_int64)]),
+        "bos_associate_bearings": (ctypes.c_int, [vp, ctypes.c_int32, _ip, _dp, _dp, ctypes.c_double, ctypes.c_int32, _ip, _dp, _dp,
+                                                   _dp, _ip, _dp, _ip]),
+        "bos_plan_mf_associate_bearings": (ctypes.c_int, [ctypes.POINTER(bos_problem), ctypes.POINTER(bos_options), _dp,
+                                                           ctypes.c_int32, _ip, _dp, _dp, ctypes.c_double, ctypes.c_int32, _ip,
+                                                           _dp, _dp, _dp, _ip, _dp]),
+        "bos_associate_bearings_timing": (ctypes.c_int, [vp, _dp, ctypes.POINTER(ctypes.c_int64)]),
+        "bos_debug_set_associate_chunk": (ctypes.c_int, [vp, ctypes.c_int64]),
+        "bos_associate_tile": (ctypes.c_int32, []),
         "bos_lm_default_options": (None, [ctypes.POINTER(bos_lm_options)]),
         "bos_cost": (ctypes.c_int, [vp, _dp, _dp, _ip]),
         "bos_optimize": (ctypes.c_int, [vp, ctypes.POINTER(bos_lm_options), ctypes.POINTER(bos_lm_result),
@@ -605,6 +615,52 @@ def plan_mf_node_covariances(P: Problem, vals, nodes, solver: int = BOS_SOLVER_S
                                               _ptr(a, ctypes.c_int32), *[_ptr(out[k], ctypes.c_double) for k in _NODE_COV_ORDER]),
            "plan_mf_node_covariances")
     return out
+
+
+ASSOC_MAX_K = 8   # include/bos.h BOS_ASSOC_MAX_K
+_ASSOC_ORDER = ("cand_landmark", "cand_nis", "cand_innovation", "cand_var", "n_inside", "nis_all")
+
+
+def _assoc_arrays(P: Problem, pose, z, omega, k: int, nis_all: bool):
+    """(pose, z, omega as arrays (omega None stays None), the output dict of an association call):
+    cand_landmark [n, k] int32, cand_nis / cand_innovation / cand_var [n, k], n_inside [n] int32, nis_all
+    [n, NL] or None. k outside 1 .. ASSOC_MAX_K is left to the library to refuse: the arrays then get one
+    column."""
+    a = np.ascontiguousarray(pose, dtype=np.int32).ravel()
+    zz = np.ascontiguousarray(z, dtype=np.float64).ravel()
+    om = None if omega is None else np.ascontiguousarray(omega, dtype=np.float64).ravel()
+    if len(zz) != len(a) or (om is not None and len(om) != len(a)):
+        raise BosError("associate bearings: pose, z and omega differ in length")
+    n, kk = len(a), k if 1 <= k <= ASSOC_MAX_K else 1
+    return a, zz, om, {"cand_landmark": np.full((n, kk), -1, dtype=np.int32), "cand_nis": np.full((n, kk), np.inf),
+                       "cand_innovation": np.zeros((n, kk)), "cand_var": np.zeros((n, kk)),
+                       "n_inside": np.zeros(n, dtype=np.int32), "nis_all": np.zeros((n, P.NL)) if nis_all else None}
+
+
+def _assoc_ptrs(out):
+    return [_ptr(out[k], ctypes.c_int32 if out[k] is not None and out[k].dtype == np.int32 else ctypes.c_double) for k in _ASSOC_ORDER]
+
+
+def plan_mf_associate_bearings(P: Problem, vals, pose, z, omega=None, gate: float = np.inf, k: int = 4,
+                               solver: int = BOS_SOLVER_SCHUR, schur_leaf: int = 0) -> dict:
+    """Host form of Solver.associate_bearings() (test hook, bos_plan_mf_associate_bearings): the node
+    column of each distinct pose over the host factorization of the H_nf whose stored entries are vals, the
+    innovations at P's state and a plain sort. Returns the dict of arrays, nis_all included (no
+    solver_info)."""
+    cs = P.c_struct()
+    v = np.ascontiguousarray(vals, dtype=np.float64)
+    a, zz, om, out = _assoc_arrays(P, pose, z, omega, k, True)
+    opt = options(solver, schur_leaf=schur_leaf)
+    _check(lib().bos_plan_mf_associate_bearings(ctypes.byref(cs), ctypes.byref(opt), _ptr(v, ctypes.c_double), len(a),
+                                                _ptr(a, ctypes.c_int32), _ptr(zz, ctypes.c_double), _ptr(om, ctypes.c_double),
+                                                gate, k, *_assoc_ptrs(out)),
+           "plan_mf_associate_bearings")
+    return out
+
+
+def associate_tile() -> int:
+    """Landmarks per workgroup of the association's first selection stage (test constant, bos_associate_tile)."""
+    return lib().bos_associate_tile()
 
 
 # columns of plan_pair_paths
@@ -1080,6 +1136,36 @@ class Solver:
                "bos_node_covariances_timing")
         return {"prepare_ms": ms[0], "jh_ms": ms[1], "factor_ms": ms[2], "selinv_ms": ms[3], "column_ms": ms[4],
                 "gather_ms": ms[5], "download_ms": ms[6], "node_bytes": nb.value}
+
+    def associate_bearings(self, pose, z, omega=None, gate: float = np.inf, k: int = 4, nis_all: bool = False) -> dict:
+        """Gates new bearings against every landmark at the current estimate (bos_associate_bearings):
+        bearing q was measured as z[q] from pose stix pose[q] with information omega[q] (None: 1). Returns
+        a dict with cand_landmark [n, k] (landmark stix, -1 padding), cand_nis [n, k] (+inf padding),
+        cand_innovation and cand_var [n, k] (e and S = var + 1 / omega of the listed landmark, 0 padding),
+        n_inside [n] (every landmark with nis <= gate), nis_all [n, NL] or None, and solver_info. The
+        listed landmarks are the k smallest NIS inside the gate, ascending by (nis, stix)."""
+        a, zz, om, out = _assoc_arrays(self.P, pose, z, omega, k, nis_all)
+        info = ctypes.c_int32(0)
+        _check(lib().bos_associate_bearings(self._h, len(a), _ptr(a, ctypes.c_int32), _ptr(zz, ctypes.c_double),
+                                            _ptr(om, ctypes.c_double), gate, k, *_assoc_ptrs(out), ctypes.byref(info)),
+               "bos_associate_bearings")
+        out["solver_info"] = info.value
+        return out
+
+    def associate_bearings_timing(self) -> dict:
+        """The last associate_bearings() call's split in ms and the feature's device bytes
+        (bos_associate_bearings_timing)."""
+        ms = np.zeros(8)
+        nb = ctypes.c_int64(0)
+        _check(lib().bos_associate_bearings_timing(self._h, _ptr(ms, ctypes.c_double), ctypes.byref(nb)),
+               "bos_associate_bearings_timing")
+        return {"prepare_ms": ms[0], "jh_ms": ms[1], "factor_ms": ms[2], "selinv_ms": ms[3], "column_ms": ms[4],
+                "nis_ms": ms[5], "select_ms": ms[6], "download_ms": ms[7], "assoc_bytes": nb.value}
+
+    def debug_set_associate_chunk(self, max_bearings: int):
+        """Test knob (bos_debug_set_associate_chunk): associate_bearings() closes a chunk at this many
+        bearings of one pose; 0 restores the byte budget."""
+        _check(lib().bos_debug_set_associate_chunk(self._h, max_bearings), "bos_debug_set_associate_chunk")
 
     def debug_set_pair_batch(self, max_distinct_nodes: int):
         """Test knob (bos_debug_set_pair_batch): pair_covariances() closes a batch at this many distinct

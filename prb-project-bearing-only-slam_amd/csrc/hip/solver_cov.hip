@@ -1,5 +1,6 @@
 // Covariances from the multifrontal factor on the C ABI handle (solver_handle.hpp): marginals, edge, pair
-// and node covariances (hip/selinv.hpp, hip/pair_cov.hpp, hip/node_cov.hpp).
+// and node covariances and the bearing association built on them (hip/selinv.hpp, hip/pair_cov.hpp,
+// hip/node_cov.hpp, hip/associate.hpp).
 #include <algorithm>
 #include <chrono>
 
@@ -332,6 +333,164 @@ int bos_node_covariances_timing(const bos_solver* s, double ms[7], int64_t* byte
     if (!s || !ms) return fail(BOS_ERR_INVALID, "null argument");
     for (int i = 0; i < 7; ++i) ms[i] = s->node_ms[i];
     if (bytes) *bytes = bos::dev::node_cov_bytes(s->node);
+    return BOS_OK;
+}
+
+int bos_associate_bearings(bos_solver* s, int32_t n_bearings, const int32_t* pose, const double* z, const double* omega, double gate,
+                           int32_t k, int32_t* cand_landmark, double* cand_nis, double* cand_innovation, double* cand_var,
+                           int32_t* n_inside, double* nis_all, int32_t* solver_info) {
+    const char* name = "bos_associate_bearings";
+    int rc;
+    if (!s) return fail(BOS_ERR_INVALID, "null handle");
+    if ((rc = require_one_gpu(s, name, true, " (a rank holds part of the factor)"))) return rc;
+    if (const char* bad = bos::assoc_bad_argument(s->NP, n_bearings, pose, z, omega, gate, k))
+        return fail(BOS_ERR_INVALID, std::string(name) + ": " + bad);
+    if (n_bearings == 0) return BOS_OK;
+    const size_t NL = (size_t)s->NL, K = (size_t)k;
+    const bool select = cand_landmark || cand_nis || cand_innovation || cand_var || n_inside;
+    const bool rows_wanted = NL > 0 && (select || nis_all);
+    HIP_TRY(hipSetDevice(s->device));
+    if (solver_info) *solver_info = 0;
+    for (double& m : s->assoc_ms) m = 0.0;
+    // a bearing's slots as they stay where nothing is listed
+    auto pad = [&](int32_t q) {
+        for (size_t j = 0; j < K; ++j) {
+            if (cand_landmark) cand_landmark[q * K + j] = -1;
+            if (cand_nis) cand_nis[q * K + j] = HUGE_VAL;
+            if (cand_innovation) cand_innovation[q * K + j] = 0.0;
+            if (cand_var) cand_var[q * K + j] = 0.0;
+        }
+        if (n_inside) n_inside[q] = 0;
+    };
+    if (s->plan.n == 0) {   // the fixed pose alone: no landmark
+        for (int32_t q = 0; q < n_bearings; ++q) pad(q);
+        return BOS_OK;
+    }
+    typedef std::chrono::steady_clock Clock;
+    auto ms_since = [](Clock::time_point t0) { return std::chrono::duration<double, std::milli>(Clock::now() - t0).count(); };
+    const auto t_prep = Clock::now();
+    // the bearings grouped by pose, the poses in the order of their first bearing, a pose's bearings in the call's
+    std::vector<int32_t> group_of((size_t)s->NP, -1), poses;
+    std::vector<std::vector<int32_t>> members;
+    for (int32_t q = 0; q < n_bearings && rows_wanted; ++q) {
+        int32_t& g = group_of[pose[q]];
+        if (g < 0) {
+            g = (int32_t)poses.size();
+            poses.push_back(pose[q]);
+            members.emplace_back();
+        }
+        members[g].push_back(q);
+    }
+    int chunk_rows = bos::dev::associate_budget_rows(s->NL);
+    if (s->assoc_chunk > 0) chunk_rows = (int)std::min<int64_t>(chunk_rows, s->assoc_chunk);
+    if (rows_wanted) {
+        std::string err;
+        if (!bos::dev::node_cov_built(s->node)) {
+            if ((rc = pair_paths_setup(s, name))) return rc;
+            if (!bos::node_cov_plan_build(s->plan, s->pair_paths, s->node_plan, err)) return fail(BOS_ERR_UNSUPPORTED, err);
+            if (!s->node) s->node = bos::dev::node_cov_create();
+            if (bos::dev::node_cov_build(s->node, s->plan, s->pair_paths, s->node_plan, err)) return fail(BOS_ERR_DEVICE, err);
+        }
+        size_t largest = 0;
+        for (const std::vector<int32_t>& m : members) largest = std::max(largest, m.size());
+        if (!s->assoc) s->assoc = bos::dev::associate_create();
+        if (bos::dev::associate_reserve(s->assoc, s->NL, (int)std::min<size_t>(largest, (size_t)chunk_rows), err))
+            return fail(BOS_ERR_DEVICE, err);
+    }
+    s->assoc_ms[0] = ms_since(t_prep);
+    // the factorization's word, read and cleared before anything reads the panels
+    int32_t info = 0;
+    if ((rc = enqueue_factorization(s, &info))) return rc;
+    s->assoc_ms[1] = elapsed(s->ev[0], s->ev[1]);
+    s->assoc_ms[2] = elapsed(s->ev[1], s->ev[2]);
+    if (info & bos::dev::kMfStall)
+        return fail(BOS_ERR_SOLVER, "sparse factorization aborted: a dataflow dependency wait timed out");
+    if (!rows_wanted) {   // no landmark, or nothing asked for
+        for (int32_t q = 0; q < n_bearings; ++q) pad(q);
+        if (solver_info) *solver_info = info;
+        return BOS_OK;
+    }
+    const double* sig = nullptr;
+    {   // the marginals' own pass on this factorization: the diagonal blocks of the projection
+        std::string err;
+        const int src = bos::dev::mf_selected_inverse(s->mf, s->plan, &sig, s->stream, err);
+        hipError_t e = hipEventRecord(s->ev[3], s->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
+        HIP_TRY(e);
+        if (src) return fail(src == -1 ? BOS_ERR_UNSUPPORTED : BOS_ERR_DEVICE, err);
+        s->assoc_ms[3] = elapsed(s->ev[2], s->ev[3]);
+    }
+    const bos::dev::MfView view = bos::dev::mf_view(s->mf);
+    const bool want[4] = {false, false, false, true};
+    std::vector<double> zc, oc, dbuf;
+    std::vector<int32_t> ibuf;
+    for (size_t g = 0; g < poses.size(); ++g) {
+        const int a = poses[g];
+        const std::vector<int32_t>& mem = members[g];
+        std::string err;
+        bos::dev::NodeCovDev col;
+        HIP_TRY(hipEventRecord(s->ev[4], s->stream));
+        int prc = bos::dev::node_cov_enqueue(s->node, view, a, a == s->plan.fixed, want, sig, s->d_pose, s->d_lm, s->stream, nullptr, &col, err);
+        if (prc) return fail(prc == -1 ? BOS_ERR_UNSUPPORTED : BOS_ERR_DEVICE, err);
+        for (size_t c0 = 0; c0 < mem.size(); c0 += (size_t)chunk_rows) {
+            const size_t rows = std::min(mem.size() - c0, (size_t)chunk_rows);
+            zc.resize(rows);
+            oc.resize(rows);
+            for (size_t i = 0; i < rows; ++i) {
+                zc[i] = z[mem[c0 + i]];
+                oc[i] = omega ? omega[mem[c0 + i]] : 1.0;
+            }
+            bos::dev::AssociateDev res;
+            prc = bos::dev::associate_enqueue(s->assoc, a, (int)rows, zc.data(), oc.data(), gate, select, col.projected_landmark, s->d_pose,
+                                              s->d_lm, s->stream, s->ev[5], s->ev[6], &res, err);
+            hipError_t e = hipEventRecord(s->ev[7], s->stream);
+            if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
+            HIP_TRY(e);
+            if (prc) return fail(prc == -1 ? BOS_ERR_UNSUPPORTED : BOS_ERR_DEVICE, err);
+            if (c0 == 0) s->assoc_ms[4] += elapsed(s->ev[4], s->ev[5]);
+            s->assoc_ms[5] += elapsed(s->ev[5], s->ev[6]);
+            s->assoc_ms[6] += elapsed(s->ev[6], s->ev[7]);
+            // the chunk's small outputs once each, then a bearing's k entries to its place in the call's order
+            const auto t_dl = Clock::now();
+            const size_t RK = rows * bos::kAssocMaxK;
+            double* const douts[3] = {cand_nis, cand_innovation, cand_var};
+            const double* const ddev[3] = {res.cand_nis, res.cand_innovation, res.cand_var};
+            dbuf.resize(RK);
+            for (int o = 0; o < 3; ++o) {
+                if (!douts[o]) continue;
+                HIP_TRY(hipMemcpy(dbuf.data(), ddev[o], RK * sizeof(double), hipMemcpyDeviceToHost));
+                for (size_t i = 0; i < rows; ++i)
+                    std::copy(dbuf.begin() + i * bos::kAssocMaxK, dbuf.begin() + i * bos::kAssocMaxK + K, douts[o] + (size_t)mem[c0 + i] * K);
+            }
+            ibuf.resize(RK);
+            if (cand_landmark) {
+                HIP_TRY(hipMemcpy(ibuf.data(), res.cand_landmark, RK * sizeof(int32_t), hipMemcpyDeviceToHost));
+                for (size_t i = 0; i < rows; ++i)
+                    std::copy(ibuf.begin() + i * bos::kAssocMaxK, ibuf.begin() + i * bos::kAssocMaxK + K, cand_landmark + (size_t)mem[c0 + i] * K);
+            }
+            if (n_inside) {
+                HIP_TRY(hipMemcpy(ibuf.data(), res.n_inside, rows * sizeof(int32_t), hipMemcpyDeviceToHost));
+                for (size_t i = 0; i < rows; ++i) n_inside[mem[c0 + i]] = ibuf[i];
+            }
+            for (size_t i = 0; i < rows && nis_all; ++i)
+                HIP_TRY(hipMemcpy(nis_all + (size_t)mem[c0 + i] * NL, res.nis + i * NL, NL * sizeof(double), hipMemcpyDeviceToHost));
+            s->assoc_ms[7] += ms_since(t_dl);
+        }
+    }
+    if (solver_info) *solver_info = info;
+    return BOS_OK;
+}
+
+int bos_associate_bearings_timing(const bos_solver* s, double ms[8], int64_t* bytes) {
+    if (!s || !ms) return fail(BOS_ERR_INVALID, "null argument");
+    for (int i = 0; i < 8; ++i) ms[i] = s->assoc_ms[i];
+    if (bytes) *bytes = bos::dev::associate_bytes(s->assoc);
+    return BOS_OK;
+}
+
+int bos_debug_set_associate_chunk(bos_solver* s, int64_t max_bearings) {
+    if (!s || max_bearings < 0) return fail(BOS_ERR_INVALID, "bad argument");
+    s->assoc_chunk = max_bearings;
     return BOS_OK;
 }
 

@@ -1,7 +1,7 @@
 // The C ABI handle (include/bos.h) and what its implementation files share: solver_create.hip (plan,
 // uploads, bos_create / bos_destroy), solver_step.hip (the GN step, its graphs and the step's entry
 // points), solver_shard.hip (the multi-rank phases and exchanges), solver_cov.hip (marginals, edge,
-// pair and node covariances) and solver_lm.hip (bos_cost / bos_optimize). The handle owns every device buffer
+// pair and node covariances, bearing association) and solver_lm.hip (bos_cost / bos_optimize). The handle owns every device buffer
 // (mem), the static plan (host/plan.hpp), the rocSOLVER refactorization state and the RCCL communicator.
 #pragma once
 
@@ -19,6 +19,7 @@
 #include "../host/bos_math.hpp"
 #include "../host/error.hpp"
 #include "../host/plan.hpp"
+#include "associate.hpp"
 #include "device_mem.hpp"
 #include "kernels.hpp"
 #include "lm.hpp"
@@ -188,6 +189,13 @@ struct bos_solver {
     bos::NodeCovPlan node_plan;
     bos::dev::NodeCov* node = nullptr;
     double node_ms[7] = {};
+    // bos_associate_bearings (hip/associate.hpp): the chunk buffers, built at the first call (with the node
+    // call's plan and arena); the last call's split (host preparation, J+H, factorization, selected inverse,
+    // column solve + gather, NIS kernel, selection, download); bos_debug_set_associate_chunk's limit (0: the
+    // byte budget alone)
+    bos::dev::Associate* assoc = nullptr;
+    double assoc_ms[8] = {};
+    int64_t assoc_chunk = 0;
     // ---- bos_cost / bos_optimize (hip/lm.hpp). The fp64 originals of what the cost pass reads and the
     // J+H keeps only in T: odometry z / information (upper triangle) and the bearing weights (has_w)
     std::vector<double> h_oz, h_oom, h_bw;

@@ -5,11 +5,13 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <memory>
 #include <stdexcept>
 #include <string>
 #include <vector>
 
 #include "../../../include/bos_host.h"
+#include "associate.hpp"
 #include "edge_cov.hpp"
 #include "node_cov.hpp"
 #include "pair_cov.hpp"
@@ -568,6 +570,59 @@ int bos_plan_mf_pair_covariances(const bos_problem* pb, const bos_options* optio
     return BOS_OK;
 }
 
+namespace {
+// What the node and association hooks share: the plan, the host factorization with its selected inverse
+// (need_sig) and the state (theta wrapped as bos_create wraps it); column(a, o): node a's root-path solve,
+// the scatter into X, the backward sweep over every front and the per-target gather and projection the
+// device kernel runs, into o.
+struct NodeColumnHost {
+    bos::ProblemIndex pi;
+    bos::Plan P;
+    bos::PairPaths pp;
+    bos::NodeCovPlan np;
+    std::vector<double> rhs, sig, pose, Y, X;
+    std::unique_ptr<bos::HostMf> M;
+    const double* lm = nullptr;
+    bool have_sig = false;
+
+    int setup(const bos_problem* pb, const bos_options* options, const double* vals, bool need_sig) {
+        const int rc = pair_plan(pb, options, pi, P, pp);
+        if (rc) return rc;
+        std::string err;
+        if (!bos::node_cov_plan_build(P, pp, np, err)) return hfail(BOS_ERR_UNSUPPORTED, err);
+        rhs.assign(P.n, 0.0);
+        M.reset(new bos::HostMf(P, vals, rhs.data()));
+        M->factor([](int) { return true; });
+        const size_t np9 = 9 * (size_t)P.NP, nl4 = 4 * (size_t)P.NL;
+        sig.resize(np9 + nl4 + 1);
+        have_sig = need_sig;
+        if (need_sig && !M->selected_inverse(sig.data(), sig.data() + np9))
+            return hfail(BOS_ERR_UNSUPPORTED, "a node's dofs are split between two supernodes");
+        pose.assign(pb->pose_xyt, pb->pose_xyt + 3 * (size_t)P.NP);
+        for (int i = 0; i < P.NP; ++i) pose[3 * i + 2] = bos::normalized_angle<double>(bos::smallest_angle<double>(pose[3 * i + 2]));
+        lm = pb->landmark_xy;
+        Y.resize(3 * (size_t)np.max_path + 1);
+        X.resize(3 * (size_t)P.n + 1);
+        return BOS_OK;
+    }
+
+    void column(int a, const bos::NodeCovOut& o) {
+        const int d = a < P.NP ? 3 : 2;
+        const bool fixed = a == P.fixed;
+        if (!fixed) {
+            bos::pair_path_solve_host(P.mf, pp, M->L.data(), pp.node_sn[a], pp.node_loc[a], d, Y.data());
+            bos::node_cov_scatter_host(P.mf, pp, P.n, pp.node_sn[a], d, Y.data(), X.data());
+            bos::node_cov_backward_host(P.mf, np, M->L.data(), d, X.data());
+        }
+        bos::NodeCovIn in;
+        in.NP = P.NP; in.NL = P.NL; in.a = a; in.d = d; in.n = P.n;
+        in.pose = pose.data(); in.lm = lm; in.X = fixed ? nullptr : X.data(); in.node_dof = P.node_dof.data();
+        in.sig = have_sig ? sig.data() : nullptr;
+        for (int u = 0; u < P.NP + P.NL; ++u) bos::node_cov_target(in, o, u);
+    }
+};
+}  // namespace
+
 // Test hook: bos_node_covariances in its literal host form (csrc/host/node_cov.hpp): the host
 // factorization, per query node the root-path solve, the scatter into X and the backward sweep over every
 // front, the host selected inverse for the diagonal blocks, and the per-target gather and projection the
@@ -580,48 +635,73 @@ int bos_plan_mf_node_covariances(const bos_problem* pb, const bos_options* optio
     if (n_nodes == 0) return BOS_OK;
     if (!bos::node_ids_valid(pb->num_poses, pb->num_landmarks, n_nodes, nodes))
         return hfail(BOS_ERR_INVALID, "bos_node_covariances: a node id outside [0, NP + NL)");
-    bos::ProblemIndex pi;
-    bos::Plan P;
-    bos::PairPaths pp;
-    const int rc = pair_plan(pb, options, pi, P, pp);
+    NodeColumnHost H;
+    const int rc = H.setup(pb, options, vals, projected_pose || projected_landmark || pose_cov || landmark_cov);
     if (rc) return rc;
-    bos::NodeCovPlan np;
-    std::string err;
-    if (!bos::node_cov_plan_build(P, pp, np, err)) return hfail(BOS_ERR_UNSUPPORTED, err);
-    const std::vector<double> rhs(P.n, 0.0);
-    bos::HostMf M(P, vals, rhs.data());
-    M.factor([](int) { return true; });
-    const size_t np9 = 9 * (size_t)P.NP, nl4 = 4 * (size_t)P.NL, nl6 = 6 * (size_t)P.NL;
-    std::vector<double> sig(np9 + nl4 + 1);
-    const bool need_sig = projected_pose || projected_landmark || pose_cov || landmark_cov;
-    if (need_sig && !M.selected_inverse(sig.data(), sig.data() + np9))
-        return hfail(BOS_ERR_UNSUPPORTED, "a node's dofs are split between two supernodes");
-    std::vector<double> pose(pb->pose_xyt, pb->pose_xyt + 3 * (size_t)P.NP);
-    for (int i = 0; i < P.NP; ++i) pose[3 * i + 2] = bos::normalized_angle<double>(bos::smallest_angle<double>(pose[3 * i + 2]));
-    std::vector<double> Y(3 * (size_t)np.max_path + 1), X(3 * (size_t)P.n + 1);
+    const size_t np9 = 9 * (size_t)H.P.NP, nl4 = 4 * (size_t)H.P.NL, nl6 = 6 * (size_t)H.P.NL;
     for (int32_t q = 0; q < n_nodes; ++q) {
-        const int a = nodes[q], d = a < P.NP ? 3 : 2;
-        const bool fixed = a == P.fixed;
-        if (!fixed) {
-            bos::pair_path_solve_host(P.mf, pp, M.L.data(), pp.node_sn[a], pp.node_loc[a], d, Y.data());
-            bos::node_cov_scatter_host(P.mf, pp, P.n, pp.node_sn[a], d, Y.data(), X.data());
-            bos::node_cov_backward_host(P.mf, np, M.L.data(), d, X.data());
-        }
-        bos::NodeCovIn in;
-        in.NP = P.NP; in.NL = P.NL; in.a = a; in.d = d; in.n = P.n;
-        in.pose = pose.data(); in.lm = pb->landmark_xy; in.X = fixed ? nullptr : X.data(); in.node_dof = P.node_dof.data();
-        in.sig = need_sig ? sig.data() : nullptr;
         bos::NodeCovOut o;
         o.cross_pose = cross_pose ? cross_pose + q * np9 : nullptr;
         o.cross_landmark = cross_landmark ? cross_landmark + q * nl6 : nullptr;
         o.projected_pose = projected_pose ? projected_pose + q * np9 : nullptr;
         o.projected_landmark = projected_landmark ? projected_landmark + q * nl4 : nullptr;
-        for (int u = 0; u < P.NP + P.NL; ++u) bos::node_cov_target(in, o, u);
+        H.column(nodes[q], o);
     }
-    if (pose_cov) std::copy(sig.begin(), sig.begin() + np9, pose_cov);
-    if (landmark_cov) std::copy(sig.begin() + np9, sig.begin() + np9 + nl4, landmark_cov);
+    if (pose_cov) std::copy(H.sig.begin(), H.sig.begin() + np9, pose_cov);
+    if (landmark_cov) std::copy(H.sig.begin() + np9, H.sig.begin() + np9 + nl4, landmark_cov);
     return BOS_OK;
 }
+
+// Test hook: bos_associate_bearings in its literal host form (csrc/host/associate.hpp): per distinct pose
+// the node hook's column for projected_landmark, per bearing e, S and nis by the shared code, then a plain
+// sort of the landmarks inside the gate by (nis, stix).
+int bos_plan_mf_associate_bearings(const bos_problem* pb, const bos_options* options, const double* vals, int32_t n_bearings,
+                                   const int32_t* pose, const double* z, const double* omega, double gate, int32_t k,
+                                   int32_t* cand_landmark, double* cand_nis, double* cand_innovation, double* cand_var,
+                                   int32_t* n_inside, double* nis_all) {
+    if (!pb || !vals || !pb->pose_xyt || (!pb->landmark_xy && pb->num_landmarks > 0)) return hfail(BOS_ERR_INVALID, "bad argument");
+    if (const char* bad = bos::assoc_bad_argument(pb->num_poses, n_bearings, pose, z, omega, gate, k))
+        return hfail(BOS_ERR_INVALID, std::string("bos_associate_bearings: ") + bad);
+    if (n_bearings == 0) return BOS_OK;
+    NodeColumnHost H;
+    const int rc = H.setup(pb, options, vals, true);
+    if (rc) return rc;
+    const size_t NL = (size_t)H.P.NL, K = (size_t)k;
+    std::vector<double> var(4 * NL + 1), row(NL + 1), e(NL + 1), S(NL + 1);
+    std::vector<int32_t> inside;
+    int last_pose = -1;
+    for (int32_t q = 0; q < n_bearings; ++q) {
+        const int a = pose[q];
+        if (a != last_pose) {   // the column depends on the pose alone
+            bos::NodeCovOut o;
+            o.projected_landmark = var.data();
+            H.column(a, o);
+            last_pose = a;
+        }
+        const bos::AssocFrame f = bos::assoc_frame(H.pose.data(), a);
+        inside.clear();
+        for (size_t l = 0; l < NL; ++l) {
+            e[l] = bos::assoc_innovation(f, H.lm[2 * l], H.lm[2 * l + 1], z[q]);
+            S[l] = bos::assoc_innovation_var(var[4 * l], omega ? omega[q] : 1.0);
+            row[l] = bos::assoc_nis(e[l], S[l]);
+            if (bos::assoc_inside(row[l], gate)) inside.push_back((int32_t)l);
+        }
+        std::sort(inside.begin(), inside.end(), [&](int32_t x, int32_t y) { return bos::assoc_less(row[x], x, row[y], y); });
+        for (size_t j = 0; j < K; ++j) {
+            const bool listed = j < inside.size();
+            const int32_t l = listed ? inside[j] : -1;
+            if (cand_landmark) cand_landmark[q * K + j] = l;
+            if (cand_nis) cand_nis[q * K + j] = listed ? row[l] : HUGE_VAL;
+            if (cand_innovation) cand_innovation[q * K + j] = listed ? e[l] : 0.0;
+            if (cand_var) cand_var[q * K + j] = listed ? S[l] : 0.0;
+        }
+        if (n_inside) n_inside[q] = (int32_t)inside.size();
+        if (nis_all) std::copy(row.begin(), row.begin() + NL, nis_all + q * NL);
+    }
+    return BOS_OK;
+}
+
+int32_t bos_associate_tile(void) { return bos::kAssocTile; }
 
 int bos_plan_pair_paths(const bos_problem* pb, const bos_options* options, int64_t n_pairs, const int32_t* node_a,
                         const int32_t* node_b, int32_t* out) {
