@@ -430,6 +430,84 @@ int bos_associate_bearings(struct bos_solver* s, int32_t n_bearings, const int32
                            const double* omega, double gate, int32_t k, int32_t* cand_landmark, double* cand_nis,
                            double* cand_innovation, double* cand_var, int32_t* n_inside, double* nis_all,
                            int32_t* solver_info);
+/* Landmark matching at the current estimate (are two landmarks really one?): each of n_queries query
+ * landmarks, stix landmark[q], gated against every other landmark on the device by the squared Mahalanobis
+ * distance of their difference. For query a = landmark[q] and target landmark stix l != a:
+ *   d  = (l_a.x - l_l.x, l_a.y - l_l.y) at the fp64 master state
+ *   C  = the 2 x 2 covariance of l_a - l_l: exactly the four numbers bos_node_covariances puts in
+ *        projected_landmark[.][l][0..3] for the query node NP + a, by the same device code, read in place;
+ *        only its lower triangle c00 = C[0], c10 = C[2], c11 = C[3] is used
+ *   d2 = d^T C^-1 d through the LDL^T of C, evaluated in this order without FP contraction:
+ *        D0 = c00, t = c10 / D0, D1 = c11 - t * c10, y1 = d1 - t * d0, d2 = (d0 * d0) / D0 + (y1 * y1) / D1;
+ *        NaN when D0 or D1 is not finite and > 0. A caller reproduces its bits from d and C.
+ * The entry l == a is NaN by definition (its C is exactly 0 by the node call's self rule).
+ * Outputs (host pointers; any may be NULL: it is neither computed nor downloaded), k in 1 .. BOS_MATCH_MAX_K:
+ *   cand_landmark [n_queries][k]     landmark stix, -1 where nothing is listed
+ *   cand_d2       [n_queries][k]     +inf where nothing is listed; bit for bit d2_all[q][cand_landmark[q][j]]
+ *   cand_diff     [n_queries][k][2]  d of the listed landmark, 0 where nothing is listed
+ *   cand_cov      [n_queries][k][4]  C of the listed landmark, 0 where nothing is listed
+ *   n_inside      [n_queries]        landmarks with d2 <= gate: all of them, not min(., k)
+ *   d2_all        [n_queries][NL]    the whole row
+ * Order and gate are those of bos_associate_bearings: the min(k, n_inside) smallest d2 among the landmarks
+ * with d2 <= gate, ascending by (d2, stix), equal d2 to the lower stix first; a d2 that is not finite is
+ * never listed and never counted. gate may be +inf.
+ * n_queries == 0 returns BOS_OK and touches nothing. BOS_ERR_INVALID, with nothing touched, for a landmark
+ * outside [0, NL), a gate that is NaN or <= 0 and k outside 1 .. BOS_MATCH_MAX_K. On a handle whose only
+ * node is the fixed pose every list is padding, every count 0 and a row NaN.
+ * Per distinct landmark: the column solve and gather of bos_node_covariances for projected_landmark alone,
+ * one kernel with a thread per target and the two selection launches of bos_associate_bearings; k entries
+ * and a count are downloaded, the row only for d2_all; a repeated query is copied on the host.
+ * H_nf, the damping, the kernel threshold, the state handling, the synchronous behaviour, *solver_info,
+ * the clearing of the pivot word, the "counts as a bos_linearize" rule and bos_get_last_dx afterwards are
+ * exactly those of bos_marginals.
+ * Exact rules: two calls give identical bits; a query's results depend neither on the other queries of the
+ * call nor on their order; a repeated query returns identical bits.
+ * The buffers (shared with bos_match_poses) are allocated at the first call of either, with those of
+ * bos_node_covariances if it has not run; a handle that never calls pays nothing.
+ * BOS_ERR_SOLVER, BOS_ERR_UNSUPPORTED and BOS_ERR_DEVICE on exactly the conditions of bos_node_covariances:
+ * the handle stays usable. */
+#define BOS_MATCH_MAX_K BOS_ASSOC_MAX_K
+int bos_match_landmarks(struct bos_solver* s, int32_t n_queries, const int32_t* landmark, double gate, int32_t k,
+                        int32_t* cand_landmark, double* cand_d2, double* cand_diff, double* cand_cov, int32_t* n_inside,
+                        double* d2_all, int32_t* solver_info);
+/* Pose matching at the current estimate (which old poses could close a loop with this one?): n_meas
+ * relative-pose measurements, measurement q = z[q] = (x, y, theta) in the frame of pose stix pose[q] with
+ * the 3 x 3 information omega[q] (row-major; omega NULL: the identity for every measurement), each gated
+ * against every pose on the device by its normalised innovation squared. For a = pose[q] and target pose u:
+ *   e   = the error of odometry_error_jacobian<double> (csrc/host/bos_math.hpp) for source a, destination u
+ *         and measurement z[q], at the fp64 master state with cos / sin computed in fp64 on every handle
+ *         (as bos_cost); z may be any finite value, it is not wrapped first
+ *   P   = the 3 x 3 projected_pose[.][u] of bos_node_covariances for the query node a, by the same device
+ *         code and with its fixed-pose and self rules, read in place; only its lower triangle is used
+ *   R   = omega[q]^-1, formed once per measurement on the host (bos_match_information_inverse, bos_host.h)
+ *   S   = P + R, entry-wise on the lower triangle
+ *   nis = e^T S^-1 e through the LDL^T of S, evaluated in this order without FP contraction:
+ *         D0 = s00, l10 = s10 / D0, l20 = s20 / D0, D1 = s11 - l10 * s10, t21 = s21 - l20 * s10,
+ *         l21 = t21 / D1, D2 = (s22 - l20 * s20) - l21 * t21,
+ *         y0 = e0, y1 = e1 - l10 * y0, y2 = (e2 - l20 * y0) - l21 * y1,
+ *         nis = ((y0 * y0) / D0 + (y1 * y1) / D1) + (y2 * y2) / D2;
+ *         NaN when a pivot is not finite and > 0. A caller reproduces its bits from e and S.
+ * u == a is evaluated like every other target: the caller knows its query.
+ * Outputs (host pointers; any may be NULL), k in 1 .. BOS_MATCH_MAX_K:
+ *   cand_pose       [n_meas][k]     pose stix, -1 where nothing is listed
+ *   cand_nis        [n_meas][k]     +inf where nothing is listed; bit for bit nis_all[q][cand_pose[q][j]]
+ *   cand_innovation [n_meas][k][3]  e of the listed pose, 0 where nothing is listed
+ *   cand_cov        [n_meas][k][9]  S of the listed pose, its lower triangle mirrored; 0 where nothing is listed
+ *   n_inside        [n_meas]        poses with nis <= gate: all of them
+ *   nis_all         [n_meas][NP]    the whole row
+ * Order, gate and padding as for bos_match_landmarks. n_meas == 0 returns BOS_OK and touches nothing.
+ * BOS_ERR_INVALID, with nothing touched, for a pose outside [0, NP), a z that is not finite, an omega that
+ * is not finite, not bit-symmetric or whose LDL^T has a pivot <= 0, a gate that is NaN or <= 0 and k outside
+ * 1 .. BOS_MATCH_MAX_K.
+ * The measurements are grouped by pose. Per distinct pose: the column solve and gather of
+ * bos_node_covariances for projected_pose alone; then, per chunk of that pose's measurements (a chunk's
+ * rows stay within 64 MiB), one kernel with a thread per target and measurement and the two selection
+ * launches. Everything else - the system, *solver_info, the exact rules (a measurement's results depend
+ * neither on the other measurements, nor on their order, nor on the chunks), the buffers, the errors - as
+ * for bos_match_landmarks. */
+int bos_match_poses(struct bos_solver* s, int32_t n_meas, const int32_t* pose, const double* z, const double* omega,
+                    double gate, int32_t k, int32_t* cand_pose, double* cand_nis, double* cand_innovation, double* cand_cov,
+                    int32_t* n_inside, double* nis_all, int32_t* solver_info);
 /*
  * Levenberg-Marquardt with on-device step control (DESIGN.md §4 "Levenberg-Marquardt"). The objective is
  *   F(x) = sum over all edges of h(rho), rho = e^T Omega e, h(rho) = rho for rho <= kt and

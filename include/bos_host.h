@@ -147,6 +147,23 @@ int bos_plan_mf_associate_bearings(const bos_problem* problem, const bos_options
  * world needs more than that to have a second tile). */
 int32_t bos_associate_tile(void);
 
+/* Test hooks: what bos_match_landmarks / bos_match_poses compute, in their literal host form: per distinct
+ * query node the column of bos_plan_mf_node_covariances for projected_landmark / projected_pose, then the
+ * differences, errors and scores by the code the device kernels run (csrc/host/match.hpp), at the problem's
+ * state, and the selection by a plain sort over (score, stix). Arguments, outputs and rules as for the two
+ * calls; any output may be NULL. No device is used. */
+int bos_plan_mf_match_landmarks(const bos_problem* problem, const bos_options* options, const double* vals, int32_t n_queries,
+                                const int32_t* landmark, double gate, int32_t k, int32_t* cand_landmark, double* cand_d2,
+                                double* cand_diff, double* cand_cov, int32_t* n_inside, double* d2_all);
+int bos_plan_mf_match_poses(const bos_problem* problem, const bos_options* options, const double* vals, int32_t n_meas,
+                            const int32_t* pose, const double* z, const double* omega, double gate, int32_t k,
+                            int32_t* cand_pose, double* cand_nis, double* cand_innovation, double* cand_cov, int32_t* n_inside,
+                            double* nis_all);
+/* R = omega^-1 as bos_match_poses forms it, bit for bit (csrc/host/match.hpp): the LDL^T of omega (row-major
+ * 3 x 3), the lower triangle of L^-T D^-1 L^-1 evaluated and mirrored. BOS_ERR_INVALID, R untouched, when
+ * omega is not finite, not bit-symmetric or has a pivot that is not positive. */
+int bos_match_information_inverse(const double omega[9], double R[9]);
+
 /* The root paths of node pairs, from the plan alone (no values, no device): out[5 * n_pairs] = per pair
  * the supernode of a, the supernode of b (-1: the fixed pose), the lowest common ancestor of the two (-1:
  * none, the nodes hang under two roots; -2: the pair involves the fixed pose), the dofs c the two paths
@@ -251,6 +268,15 @@ int bos_associate_bearings_timing(const struct bos_solver* s, double ms[8], int6
 /* Test knob: bos_associate_bearings closes a chunk at max_bearings bearings of one pose instead of at its
  * byte budget alone; 0 restores the budget. */
 int bos_debug_set_associate_chunk(struct bos_solver* s, int64_t max_bearings);
+/* Measurement helper (tools/match_time.py): the split of the last bos_match_landmarks or bos_match_poses
+ * call, whichever ran last, in the slots of bos_associate_bearings_timing: ms[8] = host preparation, J+H
+ * build, factorization, selected inverse, column solve and gather (summed over the call's distinct nodes),
+ * score kernel, selection (summed over the call's chunks) and download; *bytes (may be NULL) = bytes of the
+ * feature's own device buffers (0 before the first call). */
+int bos_match_timing(const struct bos_solver* s, double ms[8], int64_t* bytes);
+/* Test knob: bos_match_poses closes a chunk at max_rows measurements of one pose instead of at its byte
+ * budget alone; 0 restores the budget. (A landmark query is one row: it is a chunk of its own.) */
+int bos_debug_set_match_chunk(struct bos_solver* s, int64_t max_rows);
 /* Test knob: bos_pair_covariances closes a batch at max_distinct_nodes distinct nodes (at least one pair
  * per batch) instead of at its byte budget alone; 0 restores the budget. */
 int bos_debug_set_pair_batch(struct bos_solver* s, int64_t max_distinct_nodes);

@@ -64,6 +64,8 @@ EXPORTED_SYMBOLS = [
     "bos_node_covariances", "bos_plan_mf_node_covariances", "bos_node_covariances_timing",
     "bos_associate_bearings", "bos_plan_mf_associate_bearings", "bos_associate_bearings_timing",
     "bos_debug_set_associate_chunk", "bos_associate_tile",
+    "bos_match_landmarks", "bos_match_poses", "bos_plan_mf_match_landmarks", "bos_plan_mf_match_poses",
+    "bos_match_information_inverse", "bos_match_timing", "bos_debug_set_match_chunk",
 ]
 
 # bos_lm_result.reason
@@ -237,6 +239,17 @@ def lib():
         "bos_associate_bearings_timing": (ctypes.c_int, [vp, _dp, ctypes.POINTER(ctypes.c_int64)]),
         "bos_debug_set_associate_chunk": (ctypes.c_int, [vp, ctypes.c_int64]),
         "bos_associate_tile": (ctypes.c_int32, []),
+        "bos_match_landmarks": (ctypes.c_int, [vp, ctypes.c_int32, _ip, ctypes.c_double, ctypes.c_int32, _ip, _dp, _dp, _dp, _ip, _dp,
+                                               _ip]),
+        "bos_match_poses": (ctypes.c_int, [vp, ctypes.c_int32, _ip, _dp, _dp, ctypes.c_double, ctypes.c_int32, _ip, _dp, _dp, _dp, _ip,
+                                           _dp, _ip]),
+        "bos_plan_mf_match_landmarks": (ctypes.c_int, [ctypes.POINTER(bos_problem), ctypes.POINTER(bos_options), _dp, ctypes.c_int32,
+                                                       _ip, ctypes.c_double, ctypes.c_int32, _ip, _dp, _dp, _dp, _ip, _dp]),
+        "bos_plan_mf_match_poses": (ctypes.c_int, [ctypes.POINTER(bos_problem), ctypes.POINTER(bos_options), _dp, ctypes.c_int32, _ip,
+                                                   _dp, _dp, ctypes.c_double, ctypes.c_int32, _ip, _dp, _dp, _dp, _ip, _dp]),
+        "bos_match_information_inverse": (ctypes.c_int, [_dp, _dp]),
+        "bos_match_timing": (ctypes.c_int, [vp, _dp, ctypes.POINTER(ctypes.c_int64)]),
+        "bos_debug_set_match_chunk": (ctypes.c_int, [vp, ctypes.c_int64]),
         "bos_lm_default_options": (None, [ctypes.POINTER(bos_lm_options)]),
         "bos_cost": (ctypes.c_int, [vp, _dp, _dp, _ip]),
         "bos_optimize": (ctypes.c_int, [vp, ctypes.POINTER(bos_lm_options), ctypes.POINTER(bos_lm_result),
@@ -661,6 +674,82 @@ def plan_mf_associate_bearings(P: Problem, vals, pose, z, omega=None, gate: floa
 def associate_tile() -> int:
     """Landmarks per workgroup of the association's first selection stage (test constant, bos_associate_tile)."""
     return lib().bos_associate_tile()
+
+
+MATCH_MAX_K = ASSOC_MAX_K   # include/bos.h BOS_MATCH_MAX_K
+_MATCH_LM_ORDER = ("cand_landmark", "cand_d2", "cand_diff", "cand_cov", "n_inside", "d2_all")
+_MATCH_POSE_ORDER = ("cand_pose", "cand_nis", "cand_innovation", "cand_cov", "n_inside", "nis_all")
+
+
+def _match_outputs(order, n: int, k: int, N: int, dd: int, dc: int, want_all: bool) -> dict:
+    """The output dict of a matching call in the order of its C arguments: indices [n, k] int32, scores
+    [n, k], details [n, k, dd], covariances [n, k, dc], n_inside [n] int32, the rows [n, N] or None. k
+    outside 1 .. MATCH_MAX_K is left to the library to refuse: the arrays then get one column."""
+    kk = k if 1 <= k <= MATCH_MAX_K else 1
+    return {order[0]: np.full((n, kk), -1, dtype=np.int32), order[1]: np.full((n, kk), np.inf),
+            order[2]: np.zeros((n, kk, dd)), order[3]: np.zeros((n, kk, dc)), order[4]: np.zeros(n, dtype=np.int32),
+            order[5]: np.zeros((n, N)) if want_all else None}
+
+
+def _match_lm_arrays(P: Problem, landmarks, k: int, d2_all: bool):
+    a = np.ascontiguousarray(landmarks, dtype=np.int32).ravel()
+    return a, _match_outputs(_MATCH_LM_ORDER, len(a), k, P.NL, 2, 4, d2_all)
+
+
+def _match_pose_arrays(P: Problem, pose, z, omega, k: int, nis_all: bool):
+    """(pose [n], z [n, 3], omega [n, 9] or None, the output dict): one omega (3 x 3) serves every
+    measurement."""
+    a = np.ascontiguousarray(pose, dtype=np.int32).ravel()
+    zz = np.ascontiguousarray(z, dtype=np.float64).reshape(-1, 3)
+    om = None
+    if omega is not None:
+        om = np.asarray(omega, dtype=np.float64)
+        om = np.ascontiguousarray(np.broadcast_to(om.reshape(1, 9), (len(a), 9)) if om.size == 9 else om.reshape(-1, 9))
+    if len(zz) != len(a) or (om is not None and len(om) != len(a)):
+        raise BosError("match poses: pose, z and omega differ in length")
+    return a, zz, om, _match_outputs(_MATCH_POSE_ORDER, len(a), k, P.NP, 3, 9, nis_all)
+
+
+def _match_ptrs(out, order):
+    return [_ptr(out[k], ctypes.c_int32 if out[k] is not None and out[k].dtype == np.int32 else ctypes.c_double) for k in order]
+
+
+def plan_mf_match_landmarks(P: Problem, vals, landmarks, gate: float = np.inf, k: int = 4, solver: int = BOS_SOLVER_SCHUR,
+                            schur_leaf: int = 0) -> dict:
+    """Host form of Solver.match_landmarks() (test hook, bos_plan_mf_match_landmarks): the node column of
+    each query landmark over the host factorization of the H_nf whose stored entries are vals, the
+    distances at P's state and a plain sort. Returns the dict of arrays, d2_all included (no solver_info)."""
+    cs = P.c_struct()
+    v = np.ascontiguousarray(vals, dtype=np.float64)
+    a, out = _match_lm_arrays(P, landmarks, k, True)
+    opt = options(solver, schur_leaf=schur_leaf)
+    _check(lib().bos_plan_mf_match_landmarks(ctypes.byref(cs), ctypes.byref(opt), _ptr(v, ctypes.c_double), len(a),
+                                             _ptr(a, ctypes.c_int32), gate, k, *_match_ptrs(out, _MATCH_LM_ORDER)),
+           "plan_mf_match_landmarks")
+    return out
+
+
+def plan_mf_match_poses(P: Problem, vals, pose, z, omega=None, gate: float = np.inf, k: int = 4, solver: int = BOS_SOLVER_SCHUR,
+                        schur_leaf: int = 0) -> dict:
+    """Host form of Solver.match_poses() (test hook, bos_plan_mf_match_poses). Returns the dict of arrays,
+    nis_all included (no solver_info)."""
+    cs = P.c_struct()
+    v = np.ascontiguousarray(vals, dtype=np.float64)
+    a, zz, om, out = _match_pose_arrays(P, pose, z, omega, k, True)
+    opt = options(solver, schur_leaf=schur_leaf)
+    _check(lib().bos_plan_mf_match_poses(ctypes.byref(cs), ctypes.byref(opt), _ptr(v, ctypes.c_double), len(a),
+                                         _ptr(a, ctypes.c_int32), _ptr(zz, ctypes.c_double), _ptr(om, ctypes.c_double), gate, k,
+                                         *_match_ptrs(out, _MATCH_POSE_ORDER)),
+           "plan_mf_match_poses")
+    return out
+
+
+def match_information_inverse(omega) -> np.ndarray:
+    """R = omega^-1 (3 x 3) with the bits Solver.match_poses() uses (bos_match_information_inverse)."""
+    om = np.ascontiguousarray(omega, dtype=np.float64).reshape(9)
+    R = np.zeros(9)
+    _check(lib().bos_match_information_inverse(_ptr(om, ctypes.c_double), _ptr(R, ctypes.c_double)), "bos_match_information_inverse")
+    return R.reshape(3, 3)
 
 
 # columns of plan_pair_paths
@@ -1166,6 +1255,50 @@ class Solver:
         """Test knob (bos_debug_set_associate_chunk): associate_bearings() closes a chunk at this many
         bearings of one pose; 0 restores the byte budget."""
         _check(lib().bos_debug_set_associate_chunk(self._h, max_bearings), "bos_debug_set_associate_chunk")
+
+    def match_landmarks(self, landmarks, gate: float = np.inf, k: int = 4, d2_all: bool = False) -> dict:
+        """Gates each query landmark against every other landmark at the current estimate
+        (bos_match_landmarks). Returns a dict with cand_landmark [n, k] (stix, -1 padding), cand_d2 [n, k]
+        (+inf padding), cand_diff [n, k, 2] and cand_cov [n, k, 4] (d = l_a - l_l and its covariance C, 0
+        padding), n_inside [n] (every landmark with d2 <= gate), d2_all [n, NL] or None (NaN at the query
+        itself), and solver_info. The listed landmarks are the k smallest d2 inside the gate, ascending by
+        (d2, stix)."""
+        a, out = _match_lm_arrays(self.P, landmarks, k, d2_all)
+        info = ctypes.c_int32(0)
+        _check(lib().bos_match_landmarks(self._h, len(a), _ptr(a, ctypes.c_int32), gate, k, *_match_ptrs(out, _MATCH_LM_ORDER),
+                                         ctypes.byref(info)),
+               "bos_match_landmarks")
+        out["solver_info"] = info.value
+        return out
+
+    def match_poses(self, pose, z, omega=None, gate: float = np.inf, k: int = 4, nis_all: bool = False) -> dict:
+        """Gates relative-pose measurements against every pose at the current estimate (bos_match_poses):
+        measurement q is z[q] = (x, y, theta) in the frame of pose stix pose[q] with the 3 x 3 information
+        omega[q] (None: the identity; one 3 x 3 matrix serves every measurement). Returns a dict with
+        cand_pose [n, k] (stix, -1 padding), cand_nis [n, k] (+inf padding), cand_innovation [n, k, 3] and
+        cand_cov [n, k, 9] (e and S = P + omega^-1 of the listed pose, 0 padding), n_inside [n], nis_all
+        [n, NP] or None, and solver_info."""
+        a, zz, om, out = _match_pose_arrays(self.P, pose, z, omega, k, nis_all)
+        info = ctypes.c_int32(0)
+        _check(lib().bos_match_poses(self._h, len(a), _ptr(a, ctypes.c_int32), _ptr(zz, ctypes.c_double), _ptr(om, ctypes.c_double),
+                                     gate, k, *_match_ptrs(out, _MATCH_POSE_ORDER), ctypes.byref(info)),
+               "bos_match_poses")
+        out["solver_info"] = info.value
+        return out
+
+    def match_timing(self) -> dict:
+        """The split in ms of the last match_landmarks() or match_poses() call and the feature's device
+        bytes (bos_match_timing)."""
+        ms = np.zeros(8)
+        nb = ctypes.c_int64(0)
+        _check(lib().bos_match_timing(self._h, _ptr(ms, ctypes.c_double), ctypes.byref(nb)), "bos_match_timing")
+        return {"prepare_ms": ms[0], "jh_ms": ms[1], "factor_ms": ms[2], "selinv_ms": ms[3], "column_ms": ms[4],
+                "score_ms": ms[5], "select_ms": ms[6], "download_ms": ms[7], "match_bytes": nb.value}
+
+    def debug_set_match_chunk(self, max_rows: int):
+        """Test knob (bos_debug_set_match_chunk): match_poses() closes a chunk at this many measurements
+        of one pose; 0 restores the byte budget."""
+        _check(lib().bos_debug_set_match_chunk(self._h, max_rows), "bos_debug_set_match_chunk")
 
     def debug_set_pair_batch(self, max_distinct_nodes: int):
         """Test knob (bos_debug_set_pair_batch): pair_covariances() closes a batch at this many distinct

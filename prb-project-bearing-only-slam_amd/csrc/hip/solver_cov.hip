@@ -68,6 +68,18 @@ int pair_paths_setup(bos_solver* s, const char* name) {
     return BOS_OK;
 }
 
+// The node call's plan and arena, at the first call that needs a node column
+int node_cov_setup(bos_solver* s, const char* name) {
+    if (bos::dev::node_cov_built(s->node)) return BOS_OK;
+    int rc;
+    std::string err;
+    if ((rc = pair_paths_setup(s, name))) return rc;
+    if (!bos::node_cov_plan_build(s->plan, s->pair_paths, s->node_plan, err)) return fail(BOS_ERR_UNSUPPORTED, err);
+    if (!s->node) s->node = bos::dev::node_cov_create();
+    if (bos::dev::node_cov_build(s->node, s->plan, s->pair_paths, s->node_plan, err)) return fail(BOS_ERR_DEVICE, err);
+    return BOS_OK;
+}
+
 // bos_marginals (edge = nullptr) and bos_edge_covariances (edge[4] = bearing_cross, odom_cross,
 // bearing_var, odom_cov; with all four null the pass is the marginals' own)
 int covariance_pass(bos_solver* s, const char* name, double* const* edge, double* pose_cov, double* landmark_cov,
@@ -124,6 +136,170 @@ int covariance_pass(bos_solver* s, const char* name, double* const* edge, double
     } else {
         s->marg_ms[3] = dl;
         for (int i = 0; i < 3; ++i) s->marg_ms[i] = elapsed(s->ev[i], s->ev[i + 1]);
+    }
+    if (solver_info) *solver_info = info;
+    return BOS_OK;
+}
+
+// What a matching call returns (host pointers, any of them null): the lists' doubles per entry are dd
+// (detail) and dc (covariance), the device's strides kMatchDetailStride / kMatchCovStride
+struct MatchOutputs {
+    int32_t* cand_ix;
+    double *cand_score, *cand_detail, *cand_cov;
+    int32_t* n_inside;
+    double* all;
+    int dd, dc;
+};
+
+// bos_match_landmarks (zr null; node: the landmarks) and bos_match_poses (zr: [n][kMatchRowDoubles], z and
+// the lower triangle of R; node: the poses), their arguments checked. Rows are grouped by query node, the
+// nodes in the order of their first row: one column per node. A landmark's column gives one score row,
+// copied to every query of that landmark; a pose's measurements are its rows, in chunks.
+int match_pass(bos_solver* s, const char* name, int32_t n, const int32_t* node, const double* zr, double gate, int32_t k,
+               const MatchOutputs& o, int32_t* solver_info) {
+    int rc;
+    const bool poses = zr != nullptr;
+    const size_t N = (size_t)(poses ? s->NP : s->NL), K = (size_t)k;
+    const bool select = o.cand_ix || o.cand_score || o.cand_detail || o.cand_cov || o.n_inside;
+    const bool rows_wanted = select || o.all;
+    HIP_TRY(hipSetDevice(s->device));
+    if (solver_info) *solver_info = 0;
+    for (double& m : s->match_ms) m = 0.0;
+    // a query's slots as they stay where nothing is listed
+    auto pad = [&](int32_t q) {
+        for (size_t j = 0; j < K; ++j) {
+            if (o.cand_ix) o.cand_ix[q * K + j] = -1;
+            if (o.cand_score) o.cand_score[q * K + j] = HUGE_VAL;
+            if (o.cand_detail) std::fill_n(o.cand_detail + (q * K + j) * o.dd, o.dd, 0.0);
+            if (o.cand_cov) std::fill_n(o.cand_cov + (q * K + j) * o.dc, o.dc, 0.0);
+        }
+        if (o.n_inside) o.n_inside[q] = 0;
+    };
+    if (s->plan.n == 0) {   // the fixed pose alone: there is no system to take a covariance from, no score
+        for (int32_t q = 0; q < n; ++q) pad(q);
+        if (o.all) std::fill_n(o.all, (size_t)n * N, bos::match_nan());
+        return BOS_OK;
+    }
+    typedef std::chrono::steady_clock Clock;
+    auto ms_since = [](Clock::time_point t0) { return std::chrono::duration<double, std::milli>(Clock::now() - t0).count(); };
+    const auto t_prep = Clock::now();
+    std::vector<int32_t> group_of(N, -1), nodes;
+    std::vector<std::vector<int32_t>> members;
+    for (int32_t q = 0; q < n && rows_wanted; ++q) {
+        int32_t& g = group_of[node[q]];
+        if (g < 0) {
+            g = (int32_t)nodes.size();
+            nodes.push_back(node[q]);
+            members.emplace_back();
+        }
+        members[g].push_back(q);
+    }
+    const int widest = std::max(s->NP, s->NL);   // one set of buffers serves both calls
+    int chunk_rows = bos::dev::match_budget_rows(widest);
+    if (s->match_chunk > 0) chunk_rows = (int)std::min<int64_t>(chunk_rows, s->match_chunk);
+    if (rows_wanted) {
+        std::string err;
+        if ((rc = node_cov_setup(s, name))) return rc;
+        size_t largest = 1;
+        for (const std::vector<int32_t>& m : members) largest = std::max(largest, poses ? m.size() : (size_t)1);
+        if (!s->match) s->match = bos::dev::match_create();
+        if (bos::dev::match_reserve(s->match, widest, (int)std::min<size_t>(largest, (size_t)chunk_rows), err))
+            return fail(BOS_ERR_DEVICE, err);
+    }
+    s->match_ms[0] = ms_since(t_prep);
+    // the factorization's word, read and cleared before anything reads the panels
+    int32_t info = 0;
+    if ((rc = enqueue_factorization(s, &info))) return rc;
+    s->match_ms[1] = elapsed(s->ev[0], s->ev[1]);
+    s->match_ms[2] = elapsed(s->ev[1], s->ev[2]);
+    if (info & bos::dev::kMfStall)
+        return fail(BOS_ERR_SOLVER, "sparse factorization aborted: a dataflow dependency wait timed out");
+    if (!rows_wanted) {   // nothing asked for
+        if (solver_info) *solver_info = info;
+        return BOS_OK;
+    }
+    const double* sig = nullptr;
+    {   // the marginals' own pass on this factorization: the diagonal blocks of the projection
+        std::string err;
+        const int src = bos::dev::mf_selected_inverse(s->mf, s->plan, &sig, s->stream, err);
+        hipError_t e = hipEventRecord(s->ev[3], s->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
+        HIP_TRY(e);
+        if (src) return fail(src == -1 ? BOS_ERR_UNSUPPORTED : BOS_ERR_DEVICE, err);
+        s->match_ms[3] = elapsed(s->ev[2], s->ev[3]);
+    }
+    const bos::dev::MfView view = bos::dev::mf_view(s->mf);
+    const bool want[4] = {false, false, poses, !poses};
+    std::vector<double> dbuf;
+    std::vector<int32_t> ibuf;
+    std::vector<std::pair<int32_t, int32_t>> dst;   // (the chunk's row, the query that receives it)
+    for (size_t g = 0; g < nodes.size(); ++g) {
+        const int a = nodes[g], a_node = poses ? a : s->NP + a;
+        const std::vector<int32_t>& mem = members[g];
+        std::string err;
+        bos::dev::NodeCovDev col;
+        HIP_TRY(hipEventRecord(s->ev[4], s->stream));
+        int prc = bos::dev::node_cov_enqueue(s->node, view, a_node, a_node == s->plan.fixed, want, sig, s->d_pose, s->d_lm, s->stream, nullptr,
+                                             &col, err);
+        if (prc) return fail(prc == -1 ? BOS_ERR_UNSUPPORTED : BOS_ERR_DEVICE, err);
+        const size_t rows_of_node = poses ? mem.size() : 1;
+        for (size_t c0 = 0; c0 < rows_of_node; c0 += (size_t)chunk_rows) {
+            const size_t rows = std::min(rows_of_node - c0, (size_t)chunk_rows);
+            bos::dev::MatchDev res;
+            dst.clear();
+            if (poses) {
+                dbuf.resize(rows * bos::dev::kMatchRowDoubles);
+                for (size_t i = 0; i < rows; ++i) {
+                    std::copy_n(zr + (size_t)mem[c0 + i] * bos::dev::kMatchRowDoubles, bos::dev::kMatchRowDoubles,
+                                dbuf.begin() + i * bos::dev::kMatchRowDoubles);
+                    dst.emplace_back((int32_t)i, mem[c0 + i]);
+                }
+                prc = bos::dev::match_pose_enqueue(s->match, s->NP, a, (int)rows, dbuf.data(), gate, select, col.projected_pose, s->d_pose,
+                                                   s->stream, s->ev[5], s->ev[6], &res, err);
+            } else {
+                for (int32_t q : mem) dst.emplace_back(0, q);
+                prc = bos::dev::match_landmark_enqueue(s->match, s->NL, a, gate, select, col.projected_landmark, s->d_lm, s->stream,
+                                                       s->ev[5], s->ev[6], &res, err);
+            }
+            hipError_t e = hipEventRecord(s->ev[7], s->stream);
+            if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
+            HIP_TRY(e);
+            if (prc) return fail(prc == -1 ? BOS_ERR_UNSUPPORTED : BOS_ERR_DEVICE, err);
+            if (c0 == 0) s->match_ms[4] += elapsed(s->ev[4], s->ev[5]);
+            s->match_ms[5] += elapsed(s->ev[5], s->ev[6]);
+            s->match_ms[6] += elapsed(s->ev[6], s->ev[7]);
+            // the chunk's small outputs once each, then a row's k entries to the queries that receive it
+            const auto t_dl = Clock::now();
+            const size_t RK = rows * bos::kMatchMaxK;
+            double* const douts[3] = {o.cand_score, o.cand_detail, o.cand_cov};
+            const double* const ddev[3] = {res.cand_score, res.cand_detail, res.cand_cov};
+            const size_t width[3] = {1, (size_t)o.dd, (size_t)o.dc};
+            const size_t stride[3] = {1, (size_t)bos::dev::kMatchDetailStride, (size_t)bos::dev::kMatchCovStride};
+            for (int v = 0; v < 3; ++v) {
+                if (!douts[v]) continue;
+                dbuf.resize(RK * stride[v]);
+                HIP_TRY(hipMemcpy(dbuf.data(), ddev[v], RK * stride[v] * sizeof(double), hipMemcpyDeviceToHost));
+                for (const auto& rq : dst)
+                    for (size_t j = 0; j < K; ++j)
+                        std::copy_n(dbuf.begin() + ((size_t)rq.first * bos::kMatchMaxK + j) * stride[v], width[v],
+                                    douts[v] + ((size_t)rq.second * K + j) * width[v]);
+            }
+            ibuf.resize(RK);
+            if (o.cand_ix) {
+                HIP_TRY(hipMemcpy(ibuf.data(), res.cand_ix, RK * sizeof(int32_t), hipMemcpyDeviceToHost));
+                for (const auto& rq : dst) std::copy_n(ibuf.begin() + (size_t)rq.first * bos::kMatchMaxK, K, o.cand_ix + (size_t)rq.second * K);
+            }
+            if (o.n_inside) {
+                HIP_TRY(hipMemcpy(ibuf.data(), res.n_inside, rows * sizeof(int32_t), hipMemcpyDeviceToHost));
+                for (const auto& rq : dst) o.n_inside[rq.second] = ibuf[rq.first];
+            }
+            for (size_t i = 0; i < dst.size() && o.all; ++i) {
+                double* to = o.all + (size_t)dst[i].second * N;
+                if (i > 0 && dst[i].first == dst[i - 1].first) std::copy_n(o.all + (size_t)dst[i - 1].second * N, N, to);
+                else HIP_TRY(hipMemcpy(to, res.score + (size_t)dst[i].first * N, N * sizeof(double), hipMemcpyDeviceToHost));
+            }
+            s->match_ms[7] += ms_since(t_dl);
+        }
     }
     if (solver_info) *solver_info = info;
     return BOS_OK;
@@ -277,13 +453,7 @@ int bos_node_covariances(bos_solver* s, int32_t n_nodes, const int32_t* nodes, d
     typedef std::chrono::steady_clock Clock;
     auto ms_since = [](Clock::time_point t0) { return std::chrono::duration<double, std::milli>(Clock::now() - t0).count(); };
     const auto t_prep = Clock::now();
-    if (any_node && !bos::dev::node_cov_built(s->node)) {
-        std::string err;
-        if ((rc = pair_paths_setup(s, name))) return rc;
-        if (!bos::node_cov_plan_build(s->plan, s->pair_paths, s->node_plan, err)) return fail(BOS_ERR_UNSUPPORTED, err);
-        if (!s->node) s->node = bos::dev::node_cov_create();
-        if (bos::dev::node_cov_build(s->node, s->plan, s->pair_paths, s->node_plan, err)) return fail(BOS_ERR_DEVICE, err);
-    }
+    if (any_node && (rc = node_cov_setup(s, name))) return rc;
     s->node_ms[0] = ms_since(t_prep);
     // the factorization's word, read and cleared before anything reads the panels
     int32_t info = 0;
@@ -385,12 +555,7 @@ int bos_associate_bearings(bos_solver* s, int32_t n_bearings, const int32_t* pos
     if (s->assoc_chunk > 0) chunk_rows = (int)std::min<int64_t>(chunk_rows, s->assoc_chunk);
     if (rows_wanted) {
         std::string err;
-        if (!bos::dev::node_cov_built(s->node)) {
-            if ((rc = pair_paths_setup(s, name))) return rc;
-            if (!bos::node_cov_plan_build(s->plan, s->pair_paths, s->node_plan, err)) return fail(BOS_ERR_UNSUPPORTED, err);
-            if (!s->node) s->node = bos::dev::node_cov_create();
-            if (bos::dev::node_cov_build(s->node, s->plan, s->pair_paths, s->node_plan, err)) return fail(BOS_ERR_DEVICE, err);
-        }
+        if ((rc = node_cov_setup(s, name))) return rc;
         size_t largest = 0;
         for (const std::vector<int32_t>& m : members) largest = std::max(largest, m.size());
         if (!s->assoc) s->assoc = bos::dev::associate_create();
@@ -491,6 +656,55 @@ int bos_associate_bearings_timing(const bos_solver* s, double ms[8], int64_t* by
 int bos_debug_set_associate_chunk(bos_solver* s, int64_t max_bearings) {
     if (!s || max_bearings < 0) return fail(BOS_ERR_INVALID, "bad argument");
     s->assoc_chunk = max_bearings;
+    return BOS_OK;
+}
+
+int bos_match_landmarks(bos_solver* s, int32_t n_queries, const int32_t* landmark, double gate, int32_t k, int32_t* cand_landmark,
+                        double* cand_d2, double* cand_diff, double* cand_cov, int32_t* n_inside, double* d2_all, int32_t* solver_info) {
+    const char* name = "bos_match_landmarks";
+    int rc;
+    if (!s) return fail(BOS_ERR_INVALID, "null handle");
+    if ((rc = require_one_gpu(s, name, true, " (a rank holds part of the factor)"))) return rc;
+    if (const char* bad = bos::match_landmarks_bad_argument(s->NL, n_queries, landmark, gate, k))
+        return fail(BOS_ERR_INVALID, std::string(name) + ": " + bad);
+    if (n_queries == 0) return BOS_OK;
+    const MatchOutputs o = {cand_landmark, cand_d2, cand_diff, cand_cov, n_inside, d2_all, 2, 4};
+    return match_pass(s, name, n_queries, landmark, nullptr, gate, k, o, solver_info);
+}
+
+int bos_match_poses(bos_solver* s, int32_t n_meas, const int32_t* pose, const double* z, const double* omega, double gate, int32_t k,
+                    int32_t* cand_pose, double* cand_nis, double* cand_innovation, double* cand_cov, int32_t* n_inside, double* nis_all,
+                    int32_t* solver_info) {
+    const char* name = "bos_match_poses";
+    int rc;
+    if (!s) return fail(BOS_ERR_INVALID, "null handle");
+    if ((rc = require_one_gpu(s, name, true, " (a rank holds part of the factor)"))) return rc;
+    std::vector<double> R(9 * (size_t)std::max(n_meas, 0));
+    if (const char* bad = bos::match_poses_bad_argument(s->NP, n_meas, pose, z, omega, gate, k, R.data()))
+        return fail(BOS_ERR_INVALID, std::string(name) + ": " + bad);
+    if (n_meas == 0) return BOS_OK;
+    // a measurement's row as the device reads it: z, then R's lower triangle
+    std::vector<double> zr((size_t)n_meas * bos::dev::kMatchRowDoubles);
+    for (int32_t q = 0; q < n_meas; ++q) {
+        double* v = zr.data() + (size_t)q * bos::dev::kMatchRowDoubles;
+        const double* Rq = R.data() + 9 * (size_t)q;
+        std::copy_n(z + 3 * (size_t)q, 3, v);
+        v[3] = Rq[0]; v[4] = Rq[3]; v[5] = Rq[4]; v[6] = Rq[6]; v[7] = Rq[7]; v[8] = Rq[8];
+    }
+    const MatchOutputs o = {cand_pose, cand_nis, cand_innovation, cand_cov, n_inside, nis_all, 3, 9};
+    return match_pass(s, name, n_meas, pose, zr.data(), gate, k, o, solver_info);
+}
+
+int bos_match_timing(const bos_solver* s, double ms[8], int64_t* bytes) {
+    if (!s || !ms) return fail(BOS_ERR_INVALID, "null argument");
+    for (int i = 0; i < 8; ++i) ms[i] = s->match_ms[i];
+    if (bytes) *bytes = bos::dev::match_bytes(s->match);
+    return BOS_OK;
+}
+
+int bos_debug_set_match_chunk(bos_solver* s, int64_t max_rows) {
+    if (!s || max_rows < 0) return fail(BOS_ERR_INVALID, "bad argument");
+    s->match_chunk = max_rows;
     return BOS_OK;
 }
 

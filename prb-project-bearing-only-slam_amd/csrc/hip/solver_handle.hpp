@@ -1,7 +1,7 @@
 // The C ABI handle (include/bos.h) and what its implementation files share: solver_create.hip (plan,
 // uploads, bos_create / bos_destroy), solver_step.hip (the GN step, its graphs and the step's entry
 // points), solver_shard.hip (the multi-rank phases and exchanges), solver_cov.hip (marginals, edge,
-// pair and node covariances, bearing association) and solver_lm.hip (bos_cost / bos_optimize). The handle owns every device buffer
+// pair and node covariances, bearing association, node matching) and solver_lm.hip (bos_cost / bos_optimize). The handle owns every device buffer
 // (mem), the static plan (host/plan.hpp), the rocSOLVER refactorization state and the RCCL communicator.
 #pragma once
 
@@ -23,6 +23,7 @@
 #include "device_mem.hpp"
 #include "kernels.hpp"
 #include "lm.hpp"
+#include "match.hpp"
 #include "multifrontal.hpp"
 #include "node_cov.hpp"
 #include "pair_cov.hpp"
@@ -196,6 +197,12 @@ struct bos_solver {
     bos::dev::Associate* assoc = nullptr;
     double assoc_ms[8] = {};
     int64_t assoc_chunk = 0;
+    // bos_match_landmarks / bos_match_poses (hip/match.hpp): the chunk buffers, built at the first call of
+    // either; the last call's split, the association's slots with the score kernel in the NIS kernel's;
+    // bos_debug_set_match_chunk's limit (0: the byte budget alone)
+    bos::dev::Match* match = nullptr;
+    double match_ms[8] = {};
+    int64_t match_chunk = 0;
     // ---- bos_cost / bos_optimize (hip/lm.hpp). The fp64 originals of what the cost pass reads and the
     // J+H keeps only in T: odometry z / information (upper triangle) and the bearing weights (has_w)
     std::vector<double> h_oz, h_oom, h_bw;

@@ -5,6 +5,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <functional>
 #include <memory>
 #include <stdexcept>
 #include <string>
@@ -12,6 +13,7 @@
 
 #include "../../../include/bos_host.h"
 #include "associate.hpp"
+#include "match.hpp"
 #include "edge_cov.hpp"
 #include "node_cov.hpp"
 #include "pair_cov.hpp"
@@ -702,6 +704,131 @@ int bos_plan_mf_associate_bearings(const bos_problem* pb, const bos_options* opt
 }
 
 int32_t bos_associate_tile(void) { return bos::kAssocTile; }
+
+namespace {
+// What the two matching hooks share behind a query's score row: the targets inside the gate sorted by
+// (score, stix), the k first listed with their details (detail(target, out), dd doubles; cov likewise), the
+// rest of the slots padded
+struct MatchLists {
+    int32_t* cand_ix;
+    double *cand_score, *cand_detail, *cand_cov;
+    int32_t* n_inside;
+    double* all;
+    int dd, dc;
+};
+typedef std::function<void(int32_t, double*)> MatchFill;
+void match_list_row(const MatchLists& o, int32_t q, size_t N, size_t K, double gate, const std::vector<double>& row, const MatchFill& detail,
+                    const MatchFill& cov) {
+    std::vector<int32_t> inside;
+    for (size_t t = 0; t < N; ++t)
+        if (bos::assoc_inside(row[t], gate)) inside.push_back((int32_t)t);
+    std::sort(inside.begin(), inside.end(), [&](int32_t x, int32_t y) { return bos::assoc_less(row[x], x, row[y], y); });
+    for (size_t j = 0; j < K; ++j) {
+        const bool listed = j < inside.size();
+        const int32_t t = listed ? inside[j] : -1;
+        const size_t at = (size_t)q * K + j;
+        if (o.cand_ix) o.cand_ix[at] = t;
+        if (o.cand_score) o.cand_score[at] = listed ? row[t] : HUGE_VAL;
+        if (o.cand_detail) {
+            std::fill_n(o.cand_detail + at * o.dd, o.dd, 0.0);
+            if (listed) detail(t, o.cand_detail + at * o.dd);
+        }
+        if (o.cand_cov) {
+            std::fill_n(o.cand_cov + at * o.dc, o.dc, 0.0);
+            if (listed) cov(t, o.cand_cov + at * o.dc);
+        }
+    }
+    if (o.n_inside) o.n_inside[q] = (int32_t)inside.size();
+    if (o.all) std::copy(row.begin(), row.begin() + N, o.all + (size_t)q * N);
+}
+}  // namespace
+
+// Test hook: bos_match_landmarks in its literal host form (csrc/host/match.hpp): per query the node hook's
+// column for projected_landmark, d and d2 by the shared code, then a plain sort.
+int bos_plan_mf_match_landmarks(const bos_problem* pb, const bos_options* options, const double* vals, int32_t n_queries,
+                                const int32_t* landmark, double gate, int32_t k, int32_t* cand_landmark, double* cand_d2,
+                                double* cand_diff, double* cand_cov, int32_t* n_inside, double* d2_all) {
+    if (!pb || !vals || !pb->pose_xyt || (!pb->landmark_xy && pb->num_landmarks > 0)) return hfail(BOS_ERR_INVALID, "bad argument");
+    if (const char* bad = bos::match_landmarks_bad_argument(pb->num_landmarks, n_queries, landmark, gate, k))
+        return hfail(BOS_ERR_INVALID, std::string("bos_match_landmarks: ") + bad);
+    if (n_queries == 0) return BOS_OK;
+    NodeColumnHost H;
+    const int rc = H.setup(pb, options, vals, true);
+    if (rc) return rc;
+    const size_t NL = (size_t)H.P.NL;
+    const MatchLists o = {cand_landmark, cand_d2, cand_diff, cand_cov, n_inside, d2_all, 2, 4};
+    std::vector<double> C(4 * NL + 1), row(NL + 1);
+    int last = -1;
+    for (int32_t q = 0; q < n_queries; ++q) {
+        const int a = landmark[q];
+        if (a != last) {   // the column depends on the landmark alone
+            bos::NodeCovOut co;
+            co.projected_landmark = C.data();
+            H.column(H.P.NP + a, co);
+            last = a;
+        }
+        const double ax = H.lm[2 * a], ay = H.lm[2 * a + 1];
+        auto diff = [&](int32_t l, double* d) { bos::match_landmark_diff(ax, ay, H.lm[2 * l], H.lm[2 * l + 1], d); };
+        for (size_t l = 0; l < NL; ++l) {
+            double d[2];
+            diff((int32_t)l, d);
+            row[l] = (int)l == a ? bos::match_nan() : bos::match_landmark_d2(d, C[4 * l], C[4 * l + 2], C[4 * l + 3]);
+        }
+        match_list_row(o, q, NL, (size_t)k, gate, row, diff, [&](int32_t l, double* c) { std::copy_n(C.begin() + 4 * (size_t)l, 4, c); });
+    }
+    return BOS_OK;
+}
+
+// Test hook: bos_match_poses in its literal host form: per distinct pose the node hook's column for
+// projected_pose, per measurement e, S and nis by the shared code, then a plain sort.
+int bos_plan_mf_match_poses(const bos_problem* pb, const bos_options* options, const double* vals, int32_t n_meas, const int32_t* pose,
+                            const double* z, const double* omega, double gate, int32_t k, int32_t* cand_pose, double* cand_nis,
+                            double* cand_innovation, double* cand_cov, int32_t* n_inside, double* nis_all) {
+    if (!pb || !vals || !pb->pose_xyt || (!pb->landmark_xy && pb->num_landmarks > 0)) return hfail(BOS_ERR_INVALID, "bad argument");
+    std::vector<double> R(9 * (size_t)std::max(n_meas, 0));
+    if (const char* bad = bos::match_poses_bad_argument(pb->num_poses, n_meas, pose, z, omega, gate, k, R.data()))
+        return hfail(BOS_ERR_INVALID, std::string("bos_match_poses: ") + bad);
+    if (n_meas == 0) return BOS_OK;
+    NodeColumnHost H;
+    const int rc = H.setup(pb, options, vals, true);
+    if (rc) return rc;
+    const size_t NP = (size_t)H.P.NP;
+    const MatchLists o = {cand_pose, cand_nis, cand_innovation, cand_cov, n_inside, nis_all, 3, 9};
+    std::vector<double> P(9 * NP + 1), row(NP + 1);
+    int last = -1;
+    for (int32_t q = 0; q < n_meas; ++q) {
+        const int a = pose[q];
+        if (a != last) {   // the column depends on the pose alone
+            bos::NodeCovOut co;
+            co.projected_pose = P.data();
+            H.column(a, co);
+            last = a;
+        }
+        const bos::MatchFrame f = bos::match_frame(H.pose.data(), a);
+        const double* Rq = R.data() + 9 * (size_t)q;
+        const double Rl[6] = {Rq[0], Rq[3], Rq[4], Rq[6], Rq[7], Rq[8]};
+        auto error = [&](int32_t u, double* e) { bos::match_pose_error(f, H.pose[3 * u], H.pose[3 * u + 1], H.pose[3 * u + 2], z + 3 * (size_t)q, e); };
+        for (size_t u = 0; u < NP; ++u) {
+            double e[3], S[6];
+            error((int32_t)u, e);
+            bos::match_pose_S(P.data() + 9 * u, Rl, S);
+            row[u] = bos::match_pose_nis(e, S);
+        }
+        match_list_row(o, q, NP, (size_t)k, gate, row, error, [&](int32_t u, double* full) {
+            double S[6];
+            bos::match_pose_S(P.data() + 9 * (size_t)u, Rl, S);
+            bos::match_mirror(S, full);
+        });
+    }
+    return BOS_OK;
+}
+
+int bos_match_information_inverse(const double omega[9], double R[9]) {
+    if (!omega || !R) return hfail(BOS_ERR_INVALID, "null argument");
+    if (!bos::match_information_inverse(omega, R))
+        return hfail(BOS_ERR_INVALID, "bos_match_information_inverse: omega is not finite, symmetric and positive definite");
+    return BOS_OK;
+}
 
 int bos_plan_pair_paths(const bos_problem* pb, const bos_options* options, int64_t n_pairs, const int32_t* node_a,
                         const int32_t* node_b, int32_t* out) {
