@@ -508,6 +508,59 @@ int bos_match_landmarks(struct bos_solver* s, int32_t n_queries, const int32_t* 
 int bos_match_poses(struct bos_solver* s, int32_t n_meas, const int32_t* pose, const double* z, const double* omega,
                     double gate, int32_t k, int32_t* cand_pose, double* cand_nis, double* cand_innovation, double* cand_cov,
                     int32_t* n_inside, double* nis_all, int32_t* solver_info);
+/* Joint compatibility at the current estimate (Neira & Tardos' JCBB test): the joint NIS
+ *   d2 = e^T (J Sigma J^T + R)^-1 e
+ * over the stacked innovation of a hypothesis, for n_hyp hypotheses in one call. Hypothesis h consists of the
+ * pairings hyp_start[h] .. hyp_start[h + 1] - 1 (hyp_start has n_hyp + 1 entries, hyp_start[0] == 0, never
+ * decreasing); m_h is its size (at most BOS_JOINT_MAX_M, 0 allowed) and n_pair = hyp_start[n_hyp]. Pairing i
+ * means: the bearing z[i], taken from pose stix pose[i] with information omega[i] (omega NULL: 1 everywhere),
+ * is assigned to landmark stix landmark[i]. Per hypothesis, i and j its local indices:
+ *   e_i   bearing_error<double> at the fp64 master state, fp64 cos / sin on every handle: the code and the
+ *         conventions of bos_associate_bearings (z is not wrapped first)
+ *   J_i   the 1 x 5 bearing_error_jacobian<double> over [pose dofs | landmark dofs], as in bos_pair_covariances
+ *   S_ii  edge_bearing_var(Sigma_pp, Sigma_ll, Sigma_pl, J_i) + 1.0 / omega_i: bit for bit the projected[0]
+ *         bos_pair_covariances returns for the pair (pose_i, NP + landmark_i) at this state, plus
+ *         1.0 / omega_i (the same device code on the same blocks)
+ *   S_ij  (i > j) J_i C_ij J_j^T, C_ij the 5 x 5 matrix of the four blocks Sigma(p_i, p_j), Sigma(p_i, l_j),
+ *         Sigma(l_i, p_j), Sigma(l_i, l_j). Each block is exactly what bos_pair_covariances computes for that
+ *         node pair (the path solve, then the product over the common tail), read transposed where the pair
+ *         call would need the opposite order; a block that involves the fixed pose is exactly zero; a block
+ *         between a node and itself is its cov_a. Evaluation: t = C_ij J_j^T (5 entries, each an ascending
+ *         sum), then J_i t ascending, without FP contraction (csrc/host/joint.hpp joint_S_offdiag). S_ji is
+ *         the same value: S is bit-symmetric.
+ * LDL^T and the prefix NIS: right-looking, one IEEE operation at a time, without FP contraction. A is the
+ * working copy of S, y of e. For k = 0 .. m - 1: D_k = A_kk; for i > k: l_ik = A_ik / D_k; for i > k and
+ * k < j <= i: A_ij = A_ij - l_ik * A_jk (A_jk the unscaled value); for i > k: y_i = y_i - l_ik * y_k;
+ * prefix_k = prefix_{k-1} + (y_k * y_k) / D_k, prefix_{-1} = 0. From the first k whose D_k is not finite and
+ * > 0 that prefix and all later ones are NaN. A caller reproduces every bit from the returned e and S.
+ * Outputs (host pointers; any may be NULL: it is neither computed nor downloaded):
+ *   prefix_nis     [n_pair]  entry i of hypothesis h: the joint NIS of its pairings 0 .. i (one call
+ *                            evaluates a whole branch of the interpretation tree)
+ *   joint_nis      [n_hyp]   the last prefix of h; 0 for an empty hypothesis
+ *   innovation     [n_pair]  e
+ *   innovation_cov           hypothesis h's m_h x m_h block, row-major, at offset sum over g < h of m_g^2
+ *   solver_info              as in bos_marginals
+ * Exact rules: two calls give identical bits; a hypothesis's bits depend neither on the other hypotheses of
+ * the call, nor on their order, nor on the batch it lands in; a repeated hypothesis returns identical bits;
+ * the hypothesis made of the first k pairings of h returns h's prefix_nis[0 .. k - 1], h's leading k x k
+ * block of S and h's first k entries of e, bit for bit. A hypothesis may repeat a pose, a landmark or a whole
+ * pairing: R keeps S positive definite.
+ * n_hyp == 0 returns BOS_OK and touches nothing. BOS_ERR_INVALID, with nothing touched: hyp_start[0] != 0 or
+ * a decreasing hyp_start, m_h > BOS_JOINT_MAX_M, a pose outside [0, NP) or a landmark outside [0, NL), a z
+ * that is not finite, an omega that is not finite and positive.
+ * Per batch of whole consecutive hypotheses (Y slices limited to the pair call's 64 MiB; one hypothesis
+ * always runs) the host reduces the pairings to the distinct free nodes and the needed node pairs to the
+ * distinct ones; the device runs the pair call's path solve and products, then one wavefront per hypothesis
+ * that assembles S in LDS, factors it and sums the prefixes. Nothing but the outputs is downloaded.
+ * H_nf, the damping, the kernel threshold, the state handling, the synchronous behaviour, the clearing of
+ * the pivot word, the "counts as a bos_linearize" rule and bos_get_last_dx afterwards are exactly those of
+ * bos_marginals. BOS_ERR_SOLVER, BOS_ERR_UNSUPPORTED and BOS_ERR_DEVICE fire on exactly the conditions of
+ * bos_pair_covariances: the handle stays usable. The buffers are allocated at the first call; a handle that
+ * never calls pays nothing. */
+#define BOS_JOINT_MAX_M 32
+int bos_joint_compatibility(struct bos_solver* s, int32_t n_hyp, const int32_t* hyp_start, const int32_t* pose,
+                            const int32_t* landmark, const double* z, const double* omega, double* prefix_nis,
+                            double* joint_nis, double* innovation, double* innovation_cov, int32_t* solver_info);
 /*
  * Levenberg-Marquardt with on-device step control (DESIGN.md §4 "Levenberg-Marquardt"). The objective is
  *   F(x) = sum over all edges of h(rho), rho = e^T Omega e, h(rho) = rho for rho <= kt and

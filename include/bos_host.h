@@ -159,6 +159,16 @@ int bos_plan_mf_match_poses(const bos_problem* problem, const bos_options* optio
                             const int32_t* pose, const double* z, const double* omega, double gate, int32_t k,
                             int32_t* cand_pose, double* cand_nis, double* cand_innovation, double* cand_cov, int32_t* n_inside,
                             double* nis_all);
+/* Test hook: what bos_joint_compatibility computes, in its literal host form (csrc/host/joint.hpp): the host
+ * factorization, one root-path solve per distinct node and the products in row order as in
+ * bos_plan_mf_pair_covariances, then per hypothesis e, J, the entries of S through its block table, the
+ * serial LDL^T recurrence and the prefixes, all by the functions the device kernel runs, at the problem's
+ * state. Arguments, outputs and rules as for the call; any output may be NULL. max_batch > 0 closes a batch
+ * at that many hypotheses (bos_debug_set_joint_batch). No device is used. */
+int bos_plan_mf_joint_compatibility(const bos_problem* problem, const bos_options* options, const double* vals, int32_t n_hyp,
+                                    const int32_t* hyp_start, const int32_t* pose, const int32_t* landmark, const double* z,
+                                    const double* omega, int64_t max_batch, double* prefix_nis, double* joint_nis,
+                                    double* innovation, double* innovation_cov);
 /* R = omega^-1 as bos_match_poses forms it, bit for bit (csrc/host/match.hpp): the LDL^T of omega (row-major
  * 3 x 3), the lower triangle of L^-T D^-1 L^-1 evaluated and mirrored. BOS_ERR_INVALID, R untouched, when
  * omega is not finite, not bit-symmetric or has a pivot that is not positive. */
@@ -277,6 +287,14 @@ int bos_match_timing(const struct bos_solver* s, double ms[8], int64_t* bytes);
 /* Test knob: bos_match_poses closes a chunk at max_rows measurements of one pose instead of at its byte
  * budget alone; 0 restores the budget. (A landmark query is one row: it is a chunk of its own.) */
 int bos_debug_set_match_chunk(struct bos_solver* s, int64_t max_rows);
+/* Measurement helper (tools/joint_time.py): the split of the last bos_joint_compatibility call: ms[7] = host
+ * preparation and upload, J+H build, factorization, path solve, products, NIS kernel (the last three summed
+ * over the call's batches) and download; *bytes (may be NULL) = bytes of the device buffers the call uses
+ * (its own and the pair call's arena; 0 before the first call of either). */
+int bos_joint_compatibility_timing(const struct bos_solver* s, double ms[7], int64_t* bytes);
+/* Test knob: bos_joint_compatibility closes a batch at max_hypotheses hypotheses instead of at its budgets
+ * alone; 0 restores the budgets. */
+int bos_debug_set_joint_batch(struct bos_solver* s, int64_t max_hypotheses);
 /* Test knob: bos_pair_covariances closes a batch at max_distinct_nodes distinct nodes (at least one pair
  * per batch) instead of at its byte budget alone; 0 restores the budget. */
 int bos_debug_set_pair_batch(struct bos_solver* s, int64_t max_distinct_nodes);

@@ -66,6 +66,8 @@ EXPORTED_SYMBOLS = [
     "bos_debug_set_associate_chunk", "bos_associate_tile",
     "bos_match_landmarks", "bos_match_poses", "bos_plan_mf_match_landmarks", "bos_plan_mf_match_poses",
     "bos_match_information_inverse", "bos_match_timing", "bos_debug_set_match_chunk",
+    "bos_joint_compatibility", "bos_plan_mf_joint_compatibility", "bos_joint_compatibility_timing",
+    "bos_debug_set_joint_batch",
 ]
 
 # bos_lm_result.reason
@@ -250,6 +252,11 @@ def lib():
         "bos_match_information_inverse": (ctypes.c_int, [_dp, _dp]),
         "bos_match_timing": (ctypes.c_int, [vp, _dp, ctypes.POINTER(ctypes.c_int64)]),
         "bos_debug_set_match_chunk": (ctypes.c_int, [vp, ctypes.c_int64]),
+        "bos_joint_compatibility": (ctypes.c_int, [vp, ctypes.c_int32, _ip, _ip, _ip, _dp, _dp, _dp, _dp, _dp, _dp, _ip]),
+        "bos_plan_mf_joint_compatibility": (ctypes.c_int, [ctypes.POINTER(bos_problem), ctypes.POINTER(bos_options), _dp, ctypes.c_int32,
+                                                           _ip, _ip, _ip, _dp, _dp, ctypes.c_int64, _dp, _dp, _dp, _dp]),
+        "bos_joint_compatibility_timing": (ctypes.c_int, [vp, _dp, ctypes.POINTER(ctypes.c_int64)]),
+        "bos_debug_set_joint_batch": (ctypes.c_int, [vp, ctypes.c_int64]),
         "bos_lm_default_options": (None, [ctypes.POINTER(bos_lm_options)]),
         "bos_cost": (ctypes.c_int, [vp, _dp, _dp, _ip]),
         "bos_optimize": (ctypes.c_int, [vp, ctypes.POINTER(bos_lm_options), ctypes.POINTER(bos_lm_result),
@@ -674,6 +681,70 @@ def plan_mf_associate_bearings(P: Problem, vals, pose, z, omega=None, gate: floa
 def associate_tile() -> int:
     """Landmarks per workgroup of the association's first selection stage (test constant, bos_associate_tile)."""
     return lib().bos_associate_tile()
+
+
+JOINT_MAX_M = 32   # include/bos.h BOS_JOINT_MAX_M
+_JOINT_ORDER = ("prefix_nis", "joint_nis", "innovation", "innovation_cov")
+
+
+def _joint_arrays(hypotheses, z, omega, cov: bool):
+    """(hyp_start, pose, landmark, z, omega as arrays (omega None stays None), the output dict of a joint
+    compatibility call). With z None `hypotheses` is a list of (pose, landmark, z[, omega]) arrays, one tuple
+    per hypothesis (omega: all of them carry one, or none does); otherwise it is (hyp_start, pose, landmark)
+    and z / omega are the flat arrays. innovation_cov is flat here (_joint_finish splits it), None without
+    cov. Ill-formed hyp_start is left to the library to refuse."""
+    if z is None:
+        hyps = [tuple(np.atleast_1d(np.asarray(x)).ravel() for x in h) for h in hypotheses]
+        with_om = [len(h) > 3 for h in hyps]
+        if any(with_om) and not all(with_om):
+            raise BosError("joint compatibility: some hypotheses carry omega, some do not")
+        if any(len(h) < 3 or len({len(x) for x in h}) != 1 for h in hyps):
+            raise BosError("joint compatibility: a hypothesis's arrays differ in length")
+        cat = lambda i, dt: np.ascontiguousarray(np.concatenate([h[i] for h in hyps]) if hyps else [], dtype=dt)
+        start = np.zeros(len(hyps) + 1, dtype=np.int32)
+        start[1:] = np.cumsum([len(h[0]) for h in hyps])
+        a, l, zz = cat(0, np.int32), cat(1, np.int32), cat(2, np.float64)
+        om = cat(3, np.float64) if hyps and all(with_om) else None
+    else:
+        start, a, l = (np.ascontiguousarray(x, dtype=np.int32).ravel() for x in hypotheses)
+        zz = np.ascontiguousarray(z, dtype=np.float64).ravel()
+        om = None if omega is None else np.ascontiguousarray(omega, dtype=np.float64).ravel()
+        if len(start) < 1 or len(l) != len(a) or len(zz) != len(a) or (om is not None and len(om) != len(a)) or \
+                (len(start) > 1 and start[-1] != len(a)):
+            raise BosError("joint compatibility: the arrays do not match hyp_start")
+    m = np.maximum(np.diff(start.astype(np.int64)), 0)
+    out = {"prefix_nis": np.zeros(len(a)), "joint_nis": np.zeros(len(start) - 1), "innovation": np.zeros(len(a)),
+           "innovation_cov": np.zeros(int(np.sum(m * m))) if cov else None}
+    return start, a, l, zz, om, out
+
+
+def _joint_finish(start, out):
+    """innovation_cov as a list of m x m arrays (views of the flat output), and hyp_start"""
+    if out["innovation_cov"] is not None:
+        m = np.diff(start.astype(np.int64))
+        off = np.concatenate([[0], np.cumsum(m * m)])
+        flat = out["innovation_cov"]
+        out["innovation_cov"] = [flat[off[h]:off[h + 1]].reshape(m[h], m[h]) for h in range(len(m))]
+    out["hyp_start"] = start
+    return out
+
+
+def plan_mf_joint_compatibility(P: Problem, vals, hypotheses, z=None, omega=None, solver: int = BOS_SOLVER_SCHUR,
+                                schur_leaf: int = 0, max_batch: int = 0) -> dict:
+    """Host form of Solver.joint_compatibility() (test hook, bos_plan_mf_joint_compatibility): the pair hook's
+    path solves and products over the host factorization of the H_nf whose stored entries are vals, then S,
+    its LDL^T and the prefix NIS by the code the device kernel runs, at P's state. max_batch > 0 closes a
+    batch at that many hypotheses. Returns the dict of arrays, innovation_cov included (no solver_info)."""
+    cs = P.c_struct()
+    v = np.ascontiguousarray(vals, dtype=np.float64)
+    start, a, l, zz, om, out = _joint_arrays(hypotheses, z, omega, True)
+    opt = options(solver, schur_leaf=schur_leaf)
+    _check(lib().bos_plan_mf_joint_compatibility(ctypes.byref(cs), ctypes.byref(opt), _ptr(v, ctypes.c_double), len(start) - 1,
+                                                 _ptr(start, ctypes.c_int32), _ptr(a, ctypes.c_int32), _ptr(l, ctypes.c_int32),
+                                                 _ptr(zz, ctypes.c_double), _ptr(om, ctypes.c_double), max_batch,
+                                                 *[_ptr(out[k], ctypes.c_double) for k in _JOINT_ORDER]),
+           "plan_mf_joint_compatibility")
+    return _joint_finish(start, out)
 
 
 MATCH_MAX_K = ASSOC_MAX_K   # include/bos.h BOS_MATCH_MAX_K
@@ -1255,6 +1326,39 @@ class Solver:
         """Test knob (bos_debug_set_associate_chunk): associate_bearings() closes a chunk at this many
         bearings of one pose; 0 restores the byte budget."""
         _check(lib().bos_debug_set_associate_chunk(self._h, max_bearings), "bos_debug_set_associate_chunk")
+
+    def joint_compatibility(self, hypotheses, z=None, omega=None, cov: bool = False) -> dict:
+        """Joint compatibility of association hypotheses at the current estimate (bos_joint_compatibility):
+        the joint NIS e^T (J Sigma J^T + R)^-1 e over the stacked innovation of each hypothesis of at most
+        JOINT_MAX_M pairings (bearing z from pose stix `pose` assigned to landmark stix `landmark`,
+        information omega, None: 1). `hypotheses` is a list of (pose, landmark, z[, omega]) arrays, one tuple
+        per hypothesis; or, with the flat z (and omega) given, the tuple (hyp_start, pose, landmark). Returns
+        a dict with prefix_nis [n_pair] (entry i of a hypothesis: the joint NIS of its pairings 0 .. i),
+        joint_nis [n_hyp] (0 for an empty hypothesis), innovation [n_pair], innovation_cov (cov: a list of
+        m x m arrays; else None), hyp_start and solver_info."""
+        start, a, l, zz, om, out = _joint_arrays(hypotheses, z, omega, cov)
+        info = ctypes.c_int32(0)
+        _check(lib().bos_joint_compatibility(self._h, len(start) - 1, _ptr(start, ctypes.c_int32), _ptr(a, ctypes.c_int32),
+                                             _ptr(l, ctypes.c_int32), _ptr(zz, ctypes.c_double), _ptr(om, ctypes.c_double),
+                                             *[_ptr(out[k], ctypes.c_double) for k in _JOINT_ORDER], ctypes.byref(info)),
+               "bos_joint_compatibility")
+        out["solver_info"] = info.value
+        return _joint_finish(start, out)
+
+    def joint_compatibility_timing(self) -> dict:
+        """The last joint_compatibility() call's split in ms and the device bytes it uses
+        (bos_joint_compatibility_timing)."""
+        ms = np.zeros(7)
+        nb = ctypes.c_int64(0)
+        _check(lib().bos_joint_compatibility_timing(self._h, _ptr(ms, ctypes.c_double), ctypes.byref(nb)),
+               "bos_joint_compatibility_timing")
+        return {"prepare_ms": ms[0], "jh_ms": ms[1], "factor_ms": ms[2], "path_ms": ms[3], "product_ms": ms[4],
+                "nis_ms": ms[5], "download_ms": ms[6], "joint_bytes": nb.value}
+
+    def debug_set_joint_batch(self, max_hypotheses: int):
+        """Test knob (bos_debug_set_joint_batch): joint_compatibility() closes a batch at this many
+        hypotheses; 0 restores the budgets."""
+        _check(lib().bos_debug_set_joint_batch(self._h, max_hypotheses), "bos_debug_set_joint_batch")
 
     def match_landmarks(self, landmarks, gate: float = np.inf, k: int = 4, d2_all: bool = False) -> dict:
         """Gates each query landmark against every other landmark at the current estimate

@@ -260,11 +260,11 @@ void pair_cov_destroy(PairCov* p) { delete p; }
 
 int64_t pair_cov_bytes(const PairCov* p) { return p ? (int64_t)p->mem.bytes() : 0; }
 
-int pair_cov_upload(PairCov* p, const PairCovBatch& b, const bool want[4], std::string& err) {
+namespace {
+int upload_batch(PairCov* p, const PairCovBatch& b, const bool want[4], bool need_diag, bool need_cross, std::string& err) {
     // one arena: [index arrays | Y | diagonal blocks | cross blocks | outputs], every part aligned to 256 bytes
     // (an empty one keeps an element's room); it only grows
     const size_t nn = (size_t)b.n_nodes, nq = (size_t)b.n_queries;
-    const bool need_diag = want[1] || want[2] || want[3], need_cross = want[0] || want[1];
     Arena ar(true);
     ar.add(&p->y_off, b.y_off, nn);
     ar.add(&p->n_sn, b.n_sn, nn); ar.add(&p->n_loc, b.n_loc, nn); ar.add(&p->n_d, b.n_d, nn); ar.add(&p->n_len, b.n_len, nn);
@@ -295,6 +295,16 @@ int pair_cov_upload(PairCov* p, const PairCovBatch& b, const bool want[4], std::
     if (!need_cross) p->cross = nullptr;
     return 0;
 }
+}  // namespace
+
+int pair_cov_upload(PairCov* p, const PairCovBatch& b, const bool want[4], std::string& err) {
+    return upload_batch(p, b, want, want[1] || want[2] || want[3], want[0] || want[1], err);
+}
+
+int pair_cov_upload_blocks(PairCov* p, const PairCovBatch& b, std::string& err) {
+    const bool none[4] = {false, false, false, false};
+    return upload_batch(p, b, none, true, true, err);
+}
 
 hipError_t pair_path_enqueue(const MfView& v, int max_m, int n_nodes, const int32_t* n_sn, const int32_t* n_loc, const int32_t* n_d,
                              const int64_t* y_off, double* Y, hipStream_t s) {
@@ -307,10 +317,9 @@ hipError_t pair_path_enqueue(const MfView& v, int max_m, int n_nodes, const int3
     return hipGetLastError();
 }
 
-int pair_cov_enqueue(PairCov* p, const MfView& v, int max_m, int NP, const double* pose, const double* lm, hipStream_t s,
-                     hipEvent_t after_solve, PairCovOut* out, std::string& err) {
-    if (!p->arena) { err = "bos_pair_covariances: no batch uploaded"; return -1; }
-    if (max_m > kPairMaxM) { err = "bos_pair_covariances: a front of " + std::to_string(max_m) + " rows exceeds the path solve's LDS"; return -1; }
+namespace {
+// the path solve and the products of the uploaded batch
+hipError_t enqueue_blocks(PairCov* p, const MfView& v, int max_m, int NP, hipStream_t s, hipEvent_t after_solve) {
     hipError_t e = pair_path_enqueue(v, max_m, p->n_nodes, p->n_sn, p->n_loc, p->n_d, p->y_off, p->Y, s);
     if (e == hipSuccess && after_solve) e = hipEventRecord(after_solve, s);
     ProdArgs g;
@@ -326,6 +335,30 @@ int pair_cov_enqueue(PairCov* p, const MfView& v, int max_m, int NP, const doubl
         pair_product_kernel<<<(unsigned)((tasks + per - 1) / per), kProdBlock, 0, s>>>(g);
         e = hipGetLastError();
     }
+    return e;
+}
+
+int enqueue_checks(const PairCov* p, int max_m, std::string& err) {
+    if (!p->arena) { err = "bos_pair_covariances: no batch uploaded"; return -1; }
+    if (max_m > kPairMaxM) { err = "bos_pair_covariances: a front of " + std::to_string(max_m) + " rows exceeds the path solve's LDS"; return -1; }
+    return 0;
+}
+}  // namespace
+
+int pair_cov_enqueue_blocks(PairCov* p, const MfView& v, int max_m, int NP, hipStream_t s, hipEvent_t after_solve, const double** diag,
+                            const double** cross, std::string& err) {
+    if (enqueue_checks(p, max_m, err)) return -1;
+    const hipError_t e = enqueue_blocks(p, v, max_m, NP, s, after_solve);
+    if (e != hipSuccess) { err = std::string("bos_pair_covariances: launch: ") + hipGetErrorString(e); return -2; }
+    *diag = p->diag;
+    *cross = p->cross;
+    return 0;
+}
+
+int pair_cov_enqueue(PairCov* p, const MfView& v, int max_m, int NP, const double* pose, const double* lm, hipStream_t s,
+                     hipEvent_t after_solve, PairCovOut* out, std::string& err) {
+    if (enqueue_checks(p, max_m, err)) return -1;
+    hipError_t e = enqueue_blocks(p, v, max_m, NP, s, after_solve);
     if (e == hipSuccess && p->n_queries > 0) {
         PairQueryIn in;
         in.NP = NP; in.pose = pose; in.lm = lm;

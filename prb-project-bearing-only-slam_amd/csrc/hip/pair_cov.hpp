@@ -46,6 +46,9 @@ int64_t pair_cov_bytes(const PairCov* p);
 // is idle between batches). want[4]: cross, projected, cov_a, cov_b. 0; -2 with err (the byte count) when
 // the allocation fails: the arena is then empty, nothing else is touched.
 int pair_cov_upload(PairCov* p, const PairCovBatch& b, const bool want[4], std::string& err);
+// The same with no per-query output: the diagonal and cross blocks alone (bos_joint_compatibility reads
+// them on the device)
+int pair_cov_upload_blocks(PairCov* p, const PairCovBatch& b, std::string& err);
 // The path solve alone (bos_node_covariances' forward half): one wavefront per node i < n_nodes, its start
 // supernode n_sn[i], first dof inside it n_loc[i] and dofs n_d[i], its slice at Y + y_off[i]; device arrays.
 // max_m <= kPairMaxM is the caller's to check.
@@ -55,6 +58,11 @@ hipError_t pair_path_enqueue(const MfView& v, int max_m, int n_nodes, const int3
 // path solve. v: the factor's view; max_m: PairPaths::max_m (<= kPairMaxM); pose / lm: the fp64 master state.
 int pair_cov_enqueue(PairCov* p, const MfView& v, int max_m, int NP, const double* pose, const double* lm, hipStream_t s,
                      hipEvent_t after_solve, PairCovOut* out, std::string& err);
+
+// The first two kernels alone, after pair_cov_upload_blocks: *diag [9 n_nodes] and *cross [9 n_queries] are
+// the device blocks the product kernel fills (Sigma(a, a) per distinct node, Sigma(a, b) per query).
+int pair_cov_enqueue_blocks(PairCov* p, const MfView& v, int max_m, int NP, hipStream_t s, hipEvent_t after_solve, const double** diag,
+                            const double** cross, std::string& err);
 
 }  // namespace dev
 }  // namespace bos

@@ -1,6 +1,6 @@
 // Covariances from the multifrontal factor on the C ABI handle (solver_handle.hpp): marginals, edge, pair
-// and node covariances and the bearing association built on them (hip/selinv.hpp, hip/pair_cov.hpp,
-// hip/node_cov.hpp, hip/associate.hpp).
+// and node covariances and the bearing association, node matching and joint compatibility built on them
+// (hip/selinv.hpp, hip/pair_cov.hpp, hip/node_cov.hpp, hip/associate.hpp, hip/match.hpp, hip/joint.hpp).
 #include <algorithm>
 #include <chrono>
 
@@ -421,6 +421,114 @@ int bos_pair_covariances_timing(const bos_solver* s, double ms[6], int64_t* byte
     if (!s || !ms) return fail(BOS_ERR_INVALID, "null argument");
     for (int i = 0; i < 6; ++i) ms[i] = s->pair_ms[i];
     if (bytes) *bytes = bos::dev::pair_cov_bytes(s->pair);
+    return BOS_OK;
+}
+
+int bos_joint_compatibility(bos_solver* s, int32_t n_hyp, const int32_t* hyp_start, const int32_t* pose, const int32_t* landmark,
+                            const double* z, const double* omega, double* prefix_nis, double* joint_nis, double* innovation,
+                            double* innovation_cov, int32_t* solver_info) {
+    const char* name = "bos_joint_compatibility";
+    int rc;
+    if (!s) return fail(BOS_ERR_INVALID, "null handle");
+    if ((rc = require_one_gpu(s, name, true, " (a rank holds part of the factor)"))) return rc;
+    if (const char* bad = bos::joint_bad_argument(s->NP, s->NL, n_hyp, hyp_start, pose, landmark, z, omega))
+        return fail(BOS_ERR_INVALID, std::string(name) + ": " + bad);
+    if (n_hyp == 0) return BOS_OK;
+    double* const outs[4] = {prefix_nis, joint_nis, innovation, innovation_cov};
+    bool want[4];
+    for (int i = 0; i < 4; ++i) want[i] = outs[i] != nullptr;
+    HIP_TRY(hipSetDevice(s->device));
+    if (solver_info) *solver_info = 0;
+    for (double& m : s->joint_ms) m = 0.0;
+    if (s->plan.n == 0) {   // the fixed pose alone: no landmark, so every hypothesis is empty
+        if (joint_nis) std::fill(joint_nis, joint_nis + n_hyp, 0.0);
+        return BOS_OK;
+    }
+    typedef std::chrono::steady_clock Clock;
+    auto ms_since = [](Clock::time_point t0) { return std::chrono::duration<double, std::milli>(Clock::now() - t0).count(); };
+    auto t_prep = Clock::now();
+    if ((rc = pair_paths_setup(s, name))) return rc;
+    if (!s->pair) s->pair = bos::dev::pair_cov_create();
+    if (!s->joint) s->joint = bos::dev::joint_create();
+    const int32_t n_pair = hyp_start[n_hyp];
+    std::vector<double> ones;
+    if (!omega) ones.assign((size_t)n_pair + 1, 1.0);
+    const double* om = omega ? omega : ones.data();
+    s->joint_ms[0] += ms_since(t_prep);
+    // the factorization's word, read and cleared before anything reads the panels
+    int32_t info = 0;
+    if ((rc = enqueue_factorization(s, &info))) return rc;
+    s->joint_ms[1] = elapsed(s->ev[0], s->ev[1]);
+    s->joint_ms[2] = elapsed(s->ev[1], s->ev[2]);
+    if (info & bos::dev::kMfStall)
+        return fail(BOS_ERR_SOLVER, "sparse factorization aborted: a dataflow dependency wait timed out");
+    const bos::dev::MfView view = bos::dev::mf_view(s->mf);
+    const int64_t max_hyp = s->joint_batch > 0 ? s->joint_batch : bos::dev::kJointMaxHyp;
+    if (s->joint_slot_of.empty()) s->joint_slot_of.assign((size_t)s->NP + s->NL, -1);   // all -1 between batches
+    std::vector<int32_t>& slot_of = s->joint_slot_of;
+    std::vector<int32_t> local_start;
+    bos::JointBatchHost B;
+    int64_t s_done = 0;
+    for (int32_t h0 = 0; h0 < n_hyp; h0 += B.nh) {
+        t_prep = Clock::now();
+        bos::joint_batch_build(s->plan, s->pair_paths, n_hyp, hyp_start, pose, landmark, h0,
+                               bos::dev::kPairYBudgetBytes / (int64_t)sizeof(double), max_hyp, bos::dev::kPairMaxQueries, slot_of, B);
+        const bos::PairBatchHost& Q = B.pairs;
+        bos::dev::PairCovBatch b;
+        b.n_nodes = (int32_t)Q.n_node.size(); b.n_queries = Q.nq; b.y_count = Q.y_count;
+        b.y_off = Q.y_off.data(); b.n_sn = Q.n_sn.data(); b.n_loc = Q.n_loc.data(); b.n_d = Q.n_d.data(); b.n_len = Q.n_len.data();
+        b.q_a = B.pair_a.data(); b.q_b = B.pair_b.data(); b.q_slot_a = Q.q_slot_a.data(); b.q_slot_b = Q.q_slot_b.data();
+        b.q_off_a = Q.q_off_a.data(); b.q_off_b = Q.q_off_b.data(); b.q_c = Q.q_c.data();
+        std::string err;
+        int prc = bos::dev::pair_cov_upload_blocks(s->pair, b, err);
+        if (prc) return fail(prc == -1 ? BOS_ERR_UNSUPPORTED : BOS_ERR_DEVICE, err);
+        const int32_t p0 = hyp_start[h0], np = hyp_start[h0 + B.nh] - p0;
+        local_start.resize((size_t)B.nh + 1);
+        for (int32_t h = 0; h <= B.nh; ++h) local_start[h] = hyp_start[h0 + h] - p0;
+        bos::dev::JointBatch jb;
+        jb.n_hyp = B.nh; jb.n_pair = np; jb.n_entries = B.n_entries; jb.s_count = B.s_count;
+        jb.hyp_start = local_start.data(); jb.pose = pose + p0; jb.landmark = landmark + p0; jb.tab = B.tab.data();
+        jb.tab_off = B.tab_off.data(); jb.s_off = B.s_off.data(); jb.z = z + p0; jb.omega = om + p0;
+        prc = bos::dev::joint_upload(s->joint, jb, want, err);
+        if (prc) return fail(prc == -1 ? BOS_ERR_UNSUPPORTED : BOS_ERR_DEVICE, err);
+        s->joint_ms[0] += ms_since(t_prep);
+        const double *diag = nullptr, *cross = nullptr;
+        bos::dev::JointOut res;
+        HIP_TRY(hipEventRecord(s->ev[3], s->stream));
+        prc = bos::dev::pair_cov_enqueue_blocks(s->pair, view, s->pair_paths.max_m, s->NP, s->stream, s->ev[4], &diag, &cross, err);
+        hipError_t e = hipEventRecord(s->ev[5], s->stream);
+        if (!prc && e == hipSuccess) prc = bos::dev::joint_enqueue(s->joint, s->d_pose, s->d_lm, diag, cross, s->stream, &res, err);
+        if (e == hipSuccess) e = hipEventRecord(s->ev[6], s->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
+        HIP_TRY(e);
+        if (prc) return fail(prc == -1 ? BOS_ERR_UNSUPPORTED : BOS_ERR_DEVICE, err);
+        s->joint_ms[3] += elapsed(s->ev[3], s->ev[4]);
+        s->joint_ms[4] += elapsed(s->ev[4], s->ev[5]);
+        s->joint_ms[5] += elapsed(s->ev[5], s->ev[6]);
+        const auto t_dl = Clock::now();
+        const double* dev[4] = {res.prefix_nis, res.joint_nis, res.innovation, res.innovation_cov};
+        double* const dst[4] = {prefix_nis ? prefix_nis + p0 : nullptr, joint_nis ? joint_nis + h0 : nullptr,
+                                innovation ? innovation + p0 : nullptr, innovation_cov ? innovation_cov + s_done : nullptr};
+        const size_t count[4] = {(size_t)np, (size_t)B.nh, (size_t)np, (size_t)B.s_count};
+        for (int i = 0; i < 4; ++i)
+            if (want[i] && count[i]) HIP_TRY(hipMemcpy(dst[i], dev[i], count[i] * sizeof(double), hipMemcpyDeviceToHost));
+        s_done += B.s_count;
+        s->joint_ms[6] += ms_since(t_dl);
+    }
+    if (solver_info) *solver_info = info;
+    return BOS_OK;
+}
+
+int bos_joint_compatibility_timing(const bos_solver* s, double ms[7], int64_t* bytes) {
+    if (!s || !ms) return fail(BOS_ERR_INVALID, "null argument");
+    for (int i = 0; i < 7; ++i) ms[i] = s->joint_ms[i];
+    if (bytes) *bytes = bos::dev::joint_bytes(s->joint) + bos::dev::pair_cov_bytes(s->pair);
+    return BOS_OK;
+}
+
+int bos_debug_set_joint_batch(bos_solver* s, int64_t max_hypotheses) {
+    if (!s || max_hypotheses < 0) return fail(BOS_ERR_INVALID, "bos_debug_set_joint_batch: bad argument");
+    s->joint_batch = max_hypotheses;
     return BOS_OK;
 }
 

@@ -1,7 +1,7 @@
 // The C ABI handle (include/bos.h) and what its implementation files share: solver_create.hip (plan,
 // uploads, bos_create / bos_destroy), solver_step.hip (the GN step, its graphs and the step's entry
 // points), solver_shard.hip (the multi-rank phases and exchanges), solver_cov.hip (marginals, edge,
-// pair and node covariances, bearing association, node matching) and solver_lm.hip (bos_cost / bos_optimize). The handle owns every device buffer
+// pair and node covariances, bearing association, node matching, joint compatibility) and solver_lm.hip (bos_cost / bos_optimize). The handle owns every device buffer
 // (mem), the static plan (host/plan.hpp), the rocSOLVER refactorization state and the RCCL communicator.
 #pragma once
 
@@ -21,6 +21,7 @@
 #include "../host/plan.hpp"
 #include "associate.hpp"
 #include "device_mem.hpp"
+#include "joint.hpp"
 #include "kernels.hpp"
 #include "lm.hpp"
 #include "match.hpp"
@@ -203,6 +204,14 @@ struct bos_solver {
     bos::dev::Match* match = nullptr;
     double match_ms[8] = {};
     int64_t match_chunk = 0;
+    // bos_joint_compatibility (hip/joint.hpp): the batch's tables and outputs, built at the first call (with
+    // pair_paths and the pair call's arena, whose blocks it reads); the last call's split (host preparation
+    // and upload, J+H, factorization, path solve, products, NIS kernel, download);
+    // bos_debug_set_joint_batch's limit (0: the budgets alone); the batch builder's [NP + NL] scratch
+    bos::dev::Joint* joint = nullptr;
+    std::vector<int32_t> joint_slot_of;
+    double joint_ms[7] = {};
+    int64_t joint_batch = 0;
     // ---- bos_cost / bos_optimize (hip/lm.hpp). The fp64 originals of what the cost pass reads and the
     // J+H keeps only in T: odometry z / information (upper triangle) and the bearing weights (has_w)
     std::vector<double> h_oz, h_oom, h_bw;

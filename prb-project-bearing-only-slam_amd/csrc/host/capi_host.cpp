@@ -14,6 +14,7 @@
 #include "../../../include/bos_host.h"
 #include "associate.hpp"
 #include "match.hpp"
+#include "joint.hpp"
 #include "edge_cov.hpp"
 #include "node_cov.hpp"
 #include "pair_cov.hpp"
@@ -699,6 +700,88 @@ int bos_plan_mf_associate_bearings(const bos_problem* pb, const bos_options* opt
         }
         if (n_inside) n_inside[q] = (int32_t)inside.size();
         if (nis_all) std::copy(row.begin(), row.begin() + NL, nis_all + q * NL);
+    }
+    return BOS_OK;
+}
+
+// Test hook: bos_joint_compatibility in its literal host form (csrc/host/joint.hpp): the host factorization,
+// per batch the pair hook's path solves and products for the batch's distinct nodes and node pairs, then per
+// hypothesis e, J, S through its table, the serial recurrence and the prefixes, at the problem's state (theta
+// wrapped as bos_create wraps it).
+int bos_plan_mf_joint_compatibility(const bos_problem* pb, const bos_options* options, const double* vals, int32_t n_hyp,
+                                    const int32_t* hyp_start, const int32_t* pose, const int32_t* landmark, const double* z,
+                                    const double* omega, int64_t max_batch, double* prefix_nis, double* joint_nis,
+                                    double* innovation, double* innovation_cov) {
+    if (!pb || !vals || !pb->pose_xyt || (!pb->landmark_xy && pb->num_landmarks > 0) || max_batch < 0)
+        return hfail(BOS_ERR_INVALID, "bad argument");
+    if (const char* bad = bos::joint_bad_argument(pb->num_poses, pb->num_landmarks, n_hyp, hyp_start, pose, landmark, z, omega))
+        return hfail(BOS_ERR_INVALID, std::string("bos_joint_compatibility: ") + bad);
+    if (n_hyp == 0) return BOS_OK;
+    bos::ProblemIndex pi;
+    bos::Plan P;
+    bos::PairPaths pp;
+    const int rc = pair_plan(pb, options, pi, P, pp);
+    if (rc) return rc;
+    const std::vector<double> rhs(P.n, 0.0);
+    bos::HostMf M(P, vals, rhs.data());
+    M.factor([](int) { return true; });
+    std::vector<double> state(pb->pose_xyt, pb->pose_xyt + 3 * (size_t)P.NP);
+    for (int i = 0; i < P.NP; ++i) state[3 * i + 2] = bos::normalized_angle<double>(bos::smallest_angle<double>(state[3 * i + 2]));
+    std::vector<int32_t> slot_of((size_t)P.NP + P.NL, -1);
+    bos::JointBatchHost B;
+    std::vector<double> Y, diag, cross;
+    int64_t s_done = 0;
+    for (int32_t h0 = 0; h0 < n_hyp; h0 += B.nh) {
+        bos::joint_batch_build(P, pp, n_hyp, hyp_start, pose, landmark, h0, INT64_MAX, max_batch > 0 ? max_batch : INT64_MAX, INT64_MAX,
+                               slot_of, B);
+        const bos::PairBatchHost& Q = B.pairs;
+        const size_t nn = Q.n_node.size();
+        Y.assign((size_t)Q.y_count + 1, 0.0);
+        diag.assign(9 * nn + 1, 0.0);
+        cross.assign(9 * (size_t)Q.nq + 1, 0.0);
+        for (size_t i = 0; i < nn; ++i) {
+            double* Yi = Y.data() + Q.y_off[i];
+            bos::pair_path_solve_host(P.mf, pp, M.L.data(), Q.n_sn[i], Q.n_loc[i], Q.n_d[i], Yi);
+            bos::pair_product_host(Yi, 0, Q.n_d[i], Yi, 0, Q.n_d[i], Q.n_len[i], true, diag.data() + 9 * i);
+        }
+        for (int64_t q = 0; q < Q.nq; ++q) {
+            const int sa = Q.q_slot_a[q], sb = Q.q_slot_b[q];
+            const int da = B.pair_a[q] < P.NP ? 3 : 2, db = B.pair_b[q] < P.NP ? 3 : 2;
+            const bool free2 = sa >= 0 && sb >= 0;
+            bos::pair_product_host(Y.data() + (free2 ? Q.y_off[sa] : 0), Q.q_off_a[q], da, Y.data() + (free2 ? Q.y_off[sb] : 0),
+                                   Q.q_off_b[q], db, free2 ? Q.q_c[q] : 0, false, cross.data() + 9 * q);
+        }
+        for (int32_t h = h0; h < h0 + B.nh; ++h) {
+            const int32_t p0 = hyp_start[h], m = hyp_start[h + 1] - p0;
+            double J[5 * bos::kJointMaxM], om[bos::kJointMaxM], y[bos::kJointMaxM], pre[bos::kJointMaxM];
+            double A[bos::kJointMaxM * bos::kJointLd];
+            for (int32_t i = 0; i < m; ++i) {
+                y[i] = bos::joint_innovation(state.data(), pb->landmark_xy, pose[p0 + i], landmark[p0 + i], z[p0 + i], J + 5 * i);
+                om[i] = omega ? omega[p0 + i] : 1.0;
+                if (innovation) innovation[p0 + i] = y[i];
+            }
+            bos::JointEntryIn in;
+            in.pose = state.data(); in.lm = pb->landmark_xy; in.diag = diag.data(); in.cross = cross.data();
+            in.tab = B.tab.data() + 4 * B.tab_off[h - h0];
+            in.J = J; in.omega = om;
+            double* cov = innovation_cov ? innovation_cov + s_done + B.s_off[h - h0] : nullptr;
+            for (int32_t i = 0; i < m; ++i)
+                for (int32_t j = 0; j <= i; ++j) {
+                    const double v = bos::joint_S_entry(in, i, j);
+                    A[i * bos::kJointLd + j] = v;
+                    A[j * bos::kJointLd + i] = v;
+                    if (cov) {
+                        cov[i * m + j] = v;
+                        cov[j * m + i] = v;
+                    }
+                }
+            if (prefix_nis || joint_nis) {
+                bos::joint_ldl_prefix(m, A, bos::kJointLd, y, pre);
+                for (int32_t i = 0; i < m && prefix_nis; ++i) prefix_nis[p0 + i] = pre[i];
+                if (joint_nis) joint_nis[h] = m > 0 ? pre[m - 1] : 0.0;
+            }
+        }
+        s_done += B.s_count;
     }
     return BOS_OK;
 }
