@@ -561,6 +561,71 @@ int bos_match_poses(struct bos_solver* s, int32_t n_meas, const int32_t* pose, c
 int bos_joint_compatibility(struct bos_solver* s, int32_t n_hyp, const int32_t* hyp_start, const int32_t* pose,
                             const int32_t* landmark, const double* z, const double* omega, double* prefix_nis,
                             double* joint_nis, double* innovation, double* innovation_cov, int32_t* solver_info);
+/* Joint-compatibility branch and bound at the current estimate (Neira & Tardos' JCBB): per frame of new
+ * bearings, the search over the interpretation tree that bos_joint_compatibility evaluates one branch of, on
+ * the device; nothing but the winning assignment comes back. n_frames frames in one call.
+ * Frame f consists of the bearings frame_start[f] .. frame_start[f + 1] - 1 (frame_start has n_frames + 1
+ * entries, frame_start[0] == 0, never decreasing); m_f is their number (at most BOS_JCBB_MAX_BEARINGS, 0
+ * allowed) and n_bearings = frame_start[n_frames]. Bearing b has the pose stix pose[b], the measurement z[b],
+ * the information omega[b] (omega NULL: 1 everywhere) and the candidate list
+ * cand_landmark[cand_start[b] .. cand_start[b + 1]) of c_b >= 0 landmark stix in the caller's order (the order
+ * bos_associate_bearings returns is the intended one); cand_start has n_bearings + 1 entries, cand_start[0] == 0,
+ * never decreasing, and n_pairings = cand_start[n_bearings]. The frame's pairings are all its (bearing,
+ * candidate) pairs in (bearing, list position) order; their number P_f is at most BOS_JOINT_MAX_M.
+ * All-pairings system: e_all [P_f] and S_all [P_f x P_f] are exactly the innovation and innovation_cov that
+ * bos_joint_compatibility returns for the hypothesis made of the frame's pairings in that order, bit for bit
+ * (the same host preparation, the same device code per entry).
+ * Hypothesis: it assigns to each bearing one of its candidates or nothing (-1); no landmark is assigned to two
+ * bearings of the frame. Its pairings are taken in bearing order; its S and e are the corresponding principal
+ * submatrix of S_all and subvector of e_all; its prefix NIS values are those of bos_joint_compatibility's
+ * recurrence on that submatrix, bit for bit (evaluated row by row: for a fixed entry the subtractions stay in
+ * ascending k, csrc/host/jcbb.hpp).
+ * Admissible: a hypothesis of n pairings is admissible iff for every j = 1 .. n its j-th prefix NIS is finite
+ * and <= gate[j - 1]. gate has BOS_JOINT_MAX_M entries, chi^2 quantiles by degrees of freedom, each finite and
+ * > 0, or +inf. The empty hypothesis is admissible.
+ * Result of a frame: the admissible hypothesis with 1. the most pairings; 2. among those the smallest joint NIS
+ * (last prefix); 3. among those the lexicographically smallest choice vector, a bearing's choice being its list
+ * position and "nothing" ranking after every position. A total order: the result does not depend on the order
+ * of the search.
+ * The search cuts a node whose prefix NIS fails its gate or whose pivot is not finite and positive, with its
+ * subtree (prefix NIS never decreases in floating point: this is the definition, not a heuristic); a node whose
+ * pairings so far plus the later bearings that have a candidate are strictly fewer than the best count found;
+ * and, at equal potential, a node whose prefix NIS already exceeds the best NIS known at that count.
+ * Node budget: a frame's search visits at most max_nodes tree nodes (a node: a choice whose row was evaluated,
+ * or a step "nothing"); 0 means 2^22, values above 2^26 are clamped. complete[f] = 1 when the search ended by
+ * itself: the result is then the one defined above. Otherwise complete[f] = 0 and the returned hypothesis is
+ * admissible with a count of pairings that was found; it is not promised optimal.
+ * Outputs (host pointers; any may be NULL: it is neither computed nor downloaded):
+ *   assignment     [n_bearings]  the landmark stix assigned to the bearing, or -1
+ *   n_paired       [n_frames]    the result's pairings
+ *   joint_nis      [n_frames]    its joint NIS; 0 for no pairing
+ *   prefix_nis     [n_bearings]  the joint NIS of the result's pairings among the frame's bearings 0 .. b
+ *   complete       [n_frames]
+ *   innovation     [n_pairings]  e_all
+ *   innovation_cov               frame f's P_f x P_f block S_all, row-major, at offset sum over g < f of P_g^2
+ *   solver_info                  as in bos_marginals
+ * Exact rules, for frames with complete == 1: two calls give identical bits; a frame's results depend neither
+ * on the other frames of the call, nor on their order, nor on the batch it lands in; a repeated frame returns
+ * identical bits; joint_nis[f] and prefix_nis at the paired bearings are bit for bit what
+ * bos_joint_compatibility returns for the result's pairings as one hypothesis at the same state; innovation and
+ * innovation_cov are bit for bit those of the all-pairings hypothesis.
+ * n_frames == 0 returns BOS_OK and touches nothing. BOS_ERR_INVALID, with nothing touched: frame_start[0] or
+ * cand_start[0] != 0, a decreasing frame_start or cand_start, m_f > BOS_JCBB_MAX_BEARINGS, P_f >
+ * BOS_JOINT_MAX_M, a pose outside [0, NP) or a landmark outside [0, NL), a landmark listed twice for one
+ * bearing, a z that is not finite, an omega that is not finite and positive, a gate entry that is NaN or <= 0,
+ * max_nodes < 0.
+ * Per batch of whole consecutive frames (bos_joint_compatibility's batches of the all-pairings hypotheses) the
+ * device runs the pair call's path solve and products, then one wavefront per frame that assembles S_all in
+ * LDS and searches it in place. Everything else - H_nf, the damping, the kernel threshold, the state handling,
+ * the synchronous behaviour, the clearing of the pivot word, the "counts as a bos_linearize" rule,
+ * bos_get_last_dx afterwards, BOS_ERR_SOLVER, BOS_ERR_UNSUPPORTED and BOS_ERR_DEVICE - is exactly as for
+ * bos_joint_compatibility. The buffers are allocated at the first call; a handle that never calls pays
+ * nothing. */
+#define BOS_JCBB_MAX_BEARINGS 32
+int bos_jcbb(struct bos_solver* s, int32_t n_frames, const int32_t* frame_start, const int32_t* pose, const double* z,
+             const double* omega, const int32_t* cand_start, const int32_t* cand_landmark, const double* gate, int64_t max_nodes,
+             int32_t* assignment, int32_t* n_paired, double* joint_nis, double* prefix_nis, int32_t* complete, double* innovation,
+             double* innovation_cov, int32_t* solver_info);
 /*
  * Levenberg-Marquardt with on-device step control (DESIGN.md §4 "Levenberg-Marquardt"). The objective is
  *   F(x) = sum over all edges of h(rho), rho = e^T Omega e, h(rho) = rho for rho <= kt and

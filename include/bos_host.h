@@ -169,6 +169,25 @@ int bos_plan_mf_joint_compatibility(const bos_problem* problem, const bos_option
                                     const int32_t* hyp_start, const int32_t* pose, const int32_t* landmark, const double* z,
                                     const double* omega, int64_t max_batch, double* prefix_nis, double* joint_nis,
                                     double* innovation, double* innovation_cov);
+/* Test hook: the serial search of bos_jcbb (csrc/host/jcbb.hpp jcbb_search) on a given all-pairings system: one
+ * frame of m bearings with the candidate lists cand_start [m + 1] (cand_start[0] == 0) / cand_landmark [P],
+ * S_all [P x P] row-major and e_all [P], gate [BOS_JOINT_MAX_M], max_nodes as for the call. no_bound != 0
+ * switches the count and NIS bound off (the gate cut is the definition and stays). Outputs (any may be NULL):
+ * assignment [m], *n_paired, *joint_nis, prefix_nis [m], *complete, *nodes (the nodes visited). The exact
+ * oracle of the kernel's search on the kernel's own S. BOS_ERR_INVALID as for the call's lists, gates and
+ * max_nodes (landmarks only need to be >= 0). No device is used. */
+int bos_jcbb_search_host(int32_t m, const int32_t* cand_start, const int32_t* cand_landmark, const double* S_all, const double* e_all,
+                         const double* gate, int64_t max_nodes, int32_t no_bound, int32_t* assignment, int32_t* n_paired,
+                         double* joint_nis, double* prefix_nis, int32_t* complete, int64_t* nodes);
+/* Test hook: what bos_jcbb computes, in its literal host form: the frames' all-pairings hypotheses through the
+ * code of bos_plan_mf_joint_compatibility (max_batch as there), then the serial search per frame, at the
+ * problem's state. Arguments, outputs and rules as for the call; any output may be NULL; nodes [n_frames]: the
+ * nodes visited. No device is used. */
+int bos_plan_mf_jcbb(const bos_problem* problem, const bos_options* options, const double* vals, int32_t n_frames,
+                     const int32_t* frame_start, const int32_t* pose, const double* z, const double* omega, const int32_t* cand_start,
+                     const int32_t* cand_landmark, const double* gate, int64_t max_nodes, int64_t max_batch, int32_t* assignment,
+                     int32_t* n_paired, double* joint_nis, double* prefix_nis, int32_t* complete, double* innovation,
+                     double* innovation_cov, int64_t* nodes);
 /* R = omega^-1 as bos_match_poses forms it, bit for bit (csrc/host/match.hpp): the LDL^T of omega (row-major
  * 3 x 3), the lower triangle of L^-T D^-1 L^-1 evaluated and mirrored. BOS_ERR_INVALID, R untouched, when
  * omega is not finite, not bit-symmetric or has a pivot that is not positive. */
@@ -295,6 +314,16 @@ int bos_joint_compatibility_timing(const struct bos_solver* s, double ms[7], int
 /* Test knob: bos_joint_compatibility closes a batch at max_hypotheses hypotheses instead of at its budgets
  * alone; 0 restores the budgets. */
 int bos_debug_set_joint_batch(struct bos_solver* s, int64_t max_hypotheses);
+/* Measurement helper (tools/jcbb_time.py): the split of the last bos_jcbb call in the slots of
+ * bos_joint_compatibility_timing: ms[7] = host preparation and upload, J+H build, factorization, path solve,
+ * products, assembly + search kernel (the last three summed over the call's batches) and download; *bytes (may
+ * be NULL) = bytes of the device buffers the call uses (its own and the pair call's arena). nodes (may be
+ * NULL, else capacity entries): the nodes the last call's search visited per frame, for its first
+ * min(capacity, n_frames) frames; *n_frames (may be NULL): the frames of that call. */
+int bos_jcbb_timing(const struct bos_solver* s, double ms[7], int64_t* bytes, int64_t capacity, int64_t* nodes, int32_t* n_frames);
+/* Test knob: bos_jcbb closes a batch at max_frames frames instead of at its budgets alone; 0 restores the
+ * budgets. */
+int bos_debug_set_jcbb_batch(struct bos_solver* s, int64_t max_frames);
 /* Test knob: bos_pair_covariances closes a batch at max_distinct_nodes distinct nodes (at least one pair
  * per batch) instead of at its byte budget alone; 0 restores the budget. */
 int bos_debug_set_pair_batch(struct bos_solver* s, int64_t max_distinct_nodes);

@@ -68,6 +68,7 @@ EXPORTED_SYMBOLS = [
     "bos_match_information_inverse", "bos_match_timing", "bos_debug_set_match_chunk",
     "bos_joint_compatibility", "bos_plan_mf_joint_compatibility", "bos_joint_compatibility_timing",
     "bos_debug_set_joint_batch",
+    "bos_jcbb", "bos_jcbb_search_host", "bos_plan_mf_jcbb", "bos_jcbb_timing", "bos_debug_set_jcbb_batch",
 ]
 
 # bos_lm_result.reason
@@ -257,6 +258,16 @@ def lib():
                                                            _ip, _ip, _ip, _dp, _dp, ctypes.c_int64, _dp, _dp, _dp, _dp]),
         "bos_joint_compatibility_timing": (ctypes.c_int, [vp, _dp, ctypes.POINTER(ctypes.c_int64)]),
         "bos_debug_set_joint_batch": (ctypes.c_int, [vp, ctypes.c_int64]),
+        "bos_jcbb": (ctypes.c_int, [vp, ctypes.c_int32, _ip, _ip, _dp, _dp, _ip, _ip, _dp, ctypes.c_int64, _ip, _ip, _dp, _dp, _ip, _dp,
+                                    _dp, _ip]),
+        "bos_jcbb_search_host": (ctypes.c_int, [ctypes.c_int32, _ip, _ip, _dp, _dp, _dp, ctypes.c_int64, ctypes.c_int32, _ip, _ip, _dp,
+                                                _dp, _ip, ctypes.POINTER(ctypes.c_int64)]),
+        "bos_plan_mf_jcbb": (ctypes.c_int, [ctypes.POINTER(bos_problem), ctypes.POINTER(bos_options), _dp, ctypes.c_int32, _ip, _ip, _dp,
+                                            _dp, _ip, _ip, _dp, ctypes.c_int64, ctypes.c_int64, _ip, _ip, _dp, _dp, _ip, _dp, _dp,
+                                            ctypes.POINTER(ctypes.c_int64)]),
+        "bos_jcbb_timing": (ctypes.c_int, [vp, _dp, ctypes.POINTER(ctypes.c_int64), ctypes.c_int64, ctypes.POINTER(ctypes.c_int64),
+                                           _ip]),
+        "bos_debug_set_jcbb_batch": (ctypes.c_int, [vp, ctypes.c_int64]),
         "bos_lm_default_options": (None, [ctypes.POINTER(bos_lm_options)]),
         "bos_cost": (ctypes.c_int, [vp, _dp, _dp, _ip]),
         "bos_optimize": (ctypes.c_int, [vp, ctypes.POINTER(bos_lm_options), ctypes.POINTER(bos_lm_result),
@@ -745,6 +756,146 @@ def plan_mf_joint_compatibility(P: Problem, vals, hypotheses, z=None, omega=None
                                                  *[_ptr(out[k], ctypes.c_double) for k in _JOINT_ORDER]),
            "plan_mf_joint_compatibility")
     return _joint_finish(start, out)
+
+
+JCBB_MAX_BEARINGS = 32   # include/bos.h BOS_JCBB_MAX_BEARINGS
+
+
+def _jcbb_lists(candidates):
+    """(cand_start, cand_landmark) of one frame's candidate lists: a list of lists, or a 2-D array with -1
+    padding such as associate_bearings()["cand_landmark"] (the -1 entries are dropped)."""
+    lists = [np.atleast_1d(np.asarray(c, dtype=np.int64)).ravel() for c in candidates]
+    lists = [c[c != -1] for c in lists]
+    start = np.zeros(len(lists) + 1, dtype=np.int64)
+    start[1:] = np.cumsum([len(c) for c in lists])
+    return start, (np.concatenate(lists) if lists else np.zeros(0, dtype=np.int64))
+
+
+def _jcbb_arrays(frames, gate, cov: bool, detail: bool = True):
+    """(the call's input arrays as a dict, the output dict) of a jcbb call. `frames` is a list of
+    (pose, z, omega_or_None, candidates), one tuple per frame: pose [m] (or one stix for all), z [m], omega [m]
+    or None (all frames carry one, or none does) and the candidate lists (_jcbb_lists); or a dict of the raw
+    arrays frame_start, pose, z, omega (may be None), cand_start, cand_landmark, handed to the library as they
+    are. Outputs not asked for are None."""
+    if isinstance(frames, dict):
+        a = {"frame_start": np.ascontiguousarray(frames["frame_start"], dtype=np.int32).ravel(),
+             "pose": np.ascontiguousarray(frames["pose"], dtype=np.int32).ravel(),
+             "z": np.ascontiguousarray(frames["z"], dtype=np.float64).ravel(),
+             "omega": None if frames.get("omega") is None else np.ascontiguousarray(frames["omega"], dtype=np.float64).ravel(),
+             "cand_start": np.ascontiguousarray(frames["cand_start"], dtype=np.int32).ravel(),
+             "cand_landmark": np.ascontiguousarray(frames["cand_landmark"], dtype=np.int32).ravel()}
+        nb, npair = len(a["pose"]), len(a["cand_landmark"])
+        # the library has no lengths to check the ends against: frame_start must end at the bearings given and
+        # cand_start at the candidates given (a decreasing array is left to the library, which refuses it before it
+        # reads what the array indexes)
+        if len(a["frame_start"]) < 1 or len(a["z"]) != nb or (a["omega"] is not None and len(a["omega"]) != nb) or \
+                len(a["cand_start"]) != nb + 1 or \
+                (len(a["frame_start"]) > 1 and a["frame_start"][-1] != nb and np.all(np.diff(a["frame_start"]) >= 0)) or \
+                (a["cand_start"][-1] != npair and np.all(np.diff(a["cand_start"]) >= 0)):
+            raise BosError("jcbb: the ends of frame_start / cand_start do not agree with the arrays")
+    else:
+        zs = [np.atleast_1d(np.asarray(f[1], dtype=np.float64)).ravel() for f in frames]
+        poses = [np.broadcast_to(np.atleast_1d(np.asarray(f[0], dtype=np.int64)).ravel(), zs[i].shape) if np.size(f[0]) == 1
+                 else np.atleast_1d(np.asarray(f[0], dtype=np.int64)).ravel() for i, f in enumerate(frames)]
+        with_om = [f[2] is not None for f in frames]
+        if any(with_om) and not all(with_om):
+            raise BosError("jcbb: some frames carry omega, some do not")
+        oms = [np.atleast_1d(np.asarray(f[2], dtype=np.float64)).ravel() for f in frames] if frames and all(with_om) else None
+        lists = [_jcbb_lists(f[3]) for f in frames]
+        for i in range(len(frames)):
+            if len(poses[i]) != len(zs[i]) or len(lists[i][0]) != len(zs[i]) + 1 or (oms is not None and len(oms[i]) != len(zs[i])):
+                raise BosError("jcbb: a frame's arrays differ in length")
+        cat = lambda xs, dt: np.ascontiguousarray(np.concatenate(xs) if xs else [], dtype=dt)
+        frame_start = np.zeros(len(frames) + 1, dtype=np.int32)
+        frame_start[1:] = np.cumsum([len(x) for x in zs])
+        cand_start = np.zeros(int(frame_start[-1]) + 1, dtype=np.int64)
+        off = 0
+        for i, (st, _) in enumerate(lists):
+            cand_start[frame_start[i]:frame_start[i + 1] + 1] = st + off
+            off += st[-1]
+        a = {"frame_start": frame_start, "pose": cat(poses, np.int32), "z": cat(zs, np.float64),
+             "omega": None if oms is None else cat(oms, np.float64), "cand_start": cand_start.astype(np.int32),
+             "cand_landmark": cat([l for _, l in lists], np.int32)}
+        nb, npair = len(a["pose"]), len(a["cand_landmark"])
+    a["gate"] = np.ascontiguousarray(gate, dtype=np.float64).ravel()
+    if len(a["gate"]) != JOINT_MAX_M:
+        raise BosError(f"jcbb: gate needs {JOINT_MAX_M} entries")
+    nf = len(a["frame_start"]) - 1
+    fs, cs = a["frame_start"].astype(np.int64), a["cand_start"].astype(np.int64)
+    ok = len(fs) > 0 and np.all(fs >= 0) and np.all(fs <= nb)
+    pf = np.maximum(np.diff(cs[fs]), 0) if ok else np.zeros(nf, dtype=np.int64)
+    out = {"assignment": np.full(nb, -1, dtype=np.int32),
+           "n_paired": np.zeros(nf, dtype=np.int32) if detail else None,
+           "joint_nis": np.zeros(nf) if detail else None,
+           "prefix_nis": np.zeros(nb) if detail else None,
+           "complete": np.zeros(nf, dtype=np.int32) if detail else None,
+           "innovation": np.zeros(npair) if detail else None,
+           "innovation_cov": np.zeros(int(np.sum(pf * pf))) if cov else None}
+    return a, out
+
+
+def _jcbb_out_ptrs(out):
+    return [_ptr(out["assignment"], ctypes.c_int32), _ptr(out["n_paired"], ctypes.c_int32), _ptr(out["joint_nis"], ctypes.c_double),
+            _ptr(out["prefix_nis"], ctypes.c_double), _ptr(out["complete"], ctypes.c_int32), _ptr(out["innovation"], ctypes.c_double),
+            _ptr(out["innovation_cov"], ctypes.c_double)]
+
+
+def _jcbb_finish(a, out):
+    """innovation_cov as a list of P x P arrays (views of the flat output); the lists the call was given"""
+    if out["innovation_cov"] is not None:
+        pf = np.diff(a["cand_start"].astype(np.int64)[a["frame_start"]])
+        off = np.concatenate([[0], np.cumsum(pf * pf)])
+        flat = out["innovation_cov"]
+        out["innovation_cov"] = [flat[off[f]:off[f + 1]].reshape(pf[f], pf[f]) for f in range(len(pf))]
+    for k in ("frame_start", "cand_start", "cand_landmark"):
+        out[k] = a[k]
+    return out
+
+
+def jcbb_search_host(candidates, S, e, gate, max_nodes: int = 0, no_bound: bool = False) -> dict:
+    """The serial search of Solver.jcbb() on a given all-pairings system (test hook, bos_jcbb_search_host): one
+    frame with the candidate lists `candidates` (_jcbb_lists), S [P, P], e [P], gate [JOINT_MAX_M]. no_bound
+    switches the count and NIS bound off. Returns a dict with assignment [m], n_paired, joint_nis, prefix_nis
+    [m], complete and nodes (the nodes visited)."""
+    start, lm = _jcbb_lists(candidates)
+    m = len(start) - 1
+    start, lm = np.ascontiguousarray(start, dtype=np.int32), np.ascontiguousarray(lm, dtype=np.int32)
+    S = np.ascontiguousarray(S, dtype=np.float64)
+    e = np.ascontiguousarray(e, dtype=np.float64).ravel()
+    g = np.ascontiguousarray(gate, dtype=np.float64).ravel()
+    if S.size != len(lm) * len(lm) or len(e) != len(lm) or len(g) != JOINT_MAX_M:
+        raise BosError("jcbb_search_host: S, e or gate do not match the lists")
+    assignment, prefix = np.full(m, -1, dtype=np.int32), np.zeros(m)
+    n, c, nis, nodes = ctypes.c_int32(0), ctypes.c_int32(0), ctypes.c_double(0.0), ctypes.c_int64(0)
+    _check(lib().bos_jcbb_search_host(m, _ptr(start, ctypes.c_int32), _ptr(lm, ctypes.c_int32), _ptr(S, ctypes.c_double),
+                                      _ptr(e, ctypes.c_double), _ptr(g, ctypes.c_double), max_nodes, 1 if no_bound else 0,
+                                      _ptr(assignment, ctypes.c_int32), ctypes.byref(n), ctypes.byref(nis),
+                                      _ptr(prefix, ctypes.c_double), ctypes.byref(c), ctypes.byref(nodes)),
+           "jcbb_search_host")
+    return {"assignment": assignment, "n_paired": n.value, "joint_nis": nis.value, "prefix_nis": prefix, "complete": c.value,
+            "nodes": nodes.value}
+
+
+def plan_mf_jcbb(P: Problem, vals, frames, gate, max_nodes: int = 0, solver: int = BOS_SOLVER_SCHUR, schur_leaf: int = 0,
+                 max_batch: int = 0) -> dict:
+    """Host form of Solver.jcbb() (test hook, bos_plan_mf_jcbb): the frames' all-pairings hypotheses through
+    plan_mf_joint_compatibility's code over the host factorization of the H_nf whose stored entries are vals,
+    then the serial search per frame, at P's state. max_batch > 0 closes a batch at that many frames. Returns
+    the dict of Solver.jcbb(), innovation_cov included, with nodes [n_frames] and without solver_info."""
+    cs = P.c_struct()
+    v = np.ascontiguousarray(vals, dtype=np.float64)
+    a, out = _jcbb_arrays(frames, gate, True)
+    nodes = np.zeros(len(a["frame_start"]) - 1, dtype=np.int64)
+    opt = options(solver, schur_leaf=schur_leaf)
+    _check(lib().bos_plan_mf_jcbb(ctypes.byref(cs), ctypes.byref(opt), _ptr(v, ctypes.c_double), len(a["frame_start"]) - 1,
+                                  _ptr(a["frame_start"], ctypes.c_int32), _ptr(a["pose"], ctypes.c_int32),
+                                  _ptr(a["z"], ctypes.c_double), _ptr(a["omega"], ctypes.c_double),
+                                  _ptr(a["cand_start"], ctypes.c_int32), _ptr(a["cand_landmark"], ctypes.c_int32),
+                                  _ptr(a["gate"], ctypes.c_double), max_nodes, max_batch, *_jcbb_out_ptrs(out),
+                                  _ptr(nodes, ctypes.c_int64)),
+           "plan_mf_jcbb")
+    out["nodes"] = nodes
+    return _jcbb_finish(a, out)
 
 
 MATCH_MAX_K = ASSOC_MAX_K   # include/bos.h BOS_MATCH_MAX_K
@@ -1359,6 +1510,45 @@ class Solver:
         """Test knob (bos_debug_set_joint_batch): joint_compatibility() closes a batch at this many
         hypotheses; 0 restores the budgets."""
         _check(lib().bos_debug_set_joint_batch(self._h, max_hypotheses), "bos_debug_set_joint_batch")
+
+    def jcbb(self, frames, gate, max_nodes: int = 0, cov: bool = False, detail: bool = True) -> dict:
+        """Joint-compatibility branch and bound at the current estimate (bos_jcbb): per frame of at most
+        JCBB_MAX_BEARINGS new bearings with candidate lists (at most JOINT_MAX_M pairings), the admissible
+        hypothesis with the most pairings, then the smallest joint NIS, then the lexicographically smallest
+        choice vector, searched on the device. `frames` is a list of (pose, z, omega_or_None, candidates), one
+        tuple per frame; candidates is a list of lists or a 2-D array with -1 padding such as
+        associate_bearings()["cand_landmark"]. gate [JOINT_MAX_M]: chi^2 quantiles by degrees of freedom.
+        max_nodes: the node budget per frame (0: 2^22). Returns a dict with assignment [n_bearings] (landmark
+        stix or -1), n_paired, joint_nis, complete [n_frames], prefix_nis [n_bearings], innovation [n_pairings],
+        innovation_cov (cov: a list of P x P arrays; else None), frame_start, cand_start, cand_landmark and
+        solver_info. detail False: the assignment alone is computed (the other outputs are None)."""
+        a, out = _jcbb_arrays(frames, gate, cov, detail)
+        info = ctypes.c_int32(0)
+        _check(lib().bos_jcbb(self._h, len(a["frame_start"]) - 1, _ptr(a["frame_start"], ctypes.c_int32),
+                              _ptr(a["pose"], ctypes.c_int32), _ptr(a["z"], ctypes.c_double), _ptr(a["omega"], ctypes.c_double),
+                              _ptr(a["cand_start"], ctypes.c_int32), _ptr(a["cand_landmark"], ctypes.c_int32),
+                              _ptr(a["gate"], ctypes.c_double), max_nodes, *_jcbb_out_ptrs(out), ctypes.byref(info)),
+               "bos_jcbb")
+        out["solver_info"] = info.value
+        return _jcbb_finish(a, out)
+
+    def jcbb_timing(self) -> dict:
+        """The last jcbb() call's split in ms, the device bytes it uses and the nodes its search visited per
+        frame (bos_jcbb_timing)."""
+        ms = np.zeros(7)
+        nb, nf = ctypes.c_int64(0), ctypes.c_int32(0)
+        _check(lib().bos_jcbb_timing(self._h, _ptr(ms, ctypes.c_double), ctypes.byref(nb), 0, None, ctypes.byref(nf)),
+               "bos_jcbb_timing")
+        nodes = np.zeros(max(nf.value, 1), dtype=np.int64)
+        _check(lib().bos_jcbb_timing(self._h, _ptr(ms, ctypes.c_double), ctypes.byref(nb), nf.value, _ptr(nodes, ctypes.c_int64),
+                                     None), "bos_jcbb_timing")
+        return {"prepare_ms": ms[0], "jh_ms": ms[1], "factor_ms": ms[2], "path_ms": ms[3], "product_ms": ms[4],
+                "search_ms": ms[5], "download_ms": ms[6], "jcbb_bytes": nb.value, "nodes": nodes[:nf.value]}
+
+    def debug_set_jcbb_batch(self, max_frames: int):
+        """Test knob (bos_debug_set_jcbb_batch): jcbb() closes a batch at this many frames; 0 restores the
+        budgets."""
+        _check(lib().bos_debug_set_jcbb_batch(self._h, max_frames), "bos_debug_set_jcbb_batch")
 
     def match_landmarks(self, landmarks, gate: float = np.inf, k: int = 4, d2_all: bool = False) -> dict:
         """Gates each query landmark against every other landmark at the current estimate

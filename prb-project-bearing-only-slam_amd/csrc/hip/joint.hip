@@ -3,6 +3,7 @@
 // fp64; every wave works alone: no flags, waits, tickets or atomics.
 //
 // joint_nis_kernel: one wavefront (one workgroup) per hypothesis of m <= 32 pairings.
+// Stages 1 and 2 are joint_assemble (joint_stages.hpp), shared with jcbb_kernel (jcbb.hip).
 //   1. lane i < m evaluates e_i and J_i at the master state (J_i and omega_i go to LDS).
 //   2. the lanes stride over the m (m + 1) / 2 <= 528 lower entries of S: a lane gathers the entry's four
 //      blocks through the hypothesis's table (joint_S_entry) and writes the value to LDS at (i, j) and (j, i),
@@ -14,6 +15,7 @@
 //      y_k comes by v_readlane. The prefix sum is the same scalar in every lane; lane k keeps prefix_k.
 #include "joint.hpp"
 #include "device_mem.hpp"
+#include "joint_stages.hpp"
 #include "wave_util.hpp"
 
 namespace bos {
@@ -41,35 +43,7 @@ __global__ __launch_bounds__(kWave) void joint_nis_kernel(const JointArgs a) {
         if (lane == 0 && a.joint) a.joint[h] = 0.0;
         return;
     }
-    double y = 0.0;
-    if (lane < m) {
-        double J[5];
-        y = joint_innovation(a.state_pose, a.state_lm, a.pose[p0 + lane], a.landmark[p0 + lane], a.z[p0 + lane], J);
-#pragma unroll
-        for (int c = 0; c < 5; ++c) Jl[5 * lane + c] = J[c];
-        om[lane] = a.omega[p0 + lane];
-        if (a.innovation) a.innovation[p0 + lane] = y;
-    }
-    __syncthreads();
-    JointEntryIn in;
-    in.pose = a.state_pose; in.lm = a.state_lm; in.diag = a.diag; in.cross = a.cross;
-    in.tab = a.tab + 4 * a.tab_off[h];
-    in.J = Jl; in.omega = om;
-    double* cov = a.cov ? a.cov + a.s_off[h] : nullptr;
-    const int entries = m * (m + 1) / 2;
-    for (int idx = lane; idx < entries; idx += kWave) {
-        int i = (int)((sqrtf(8.0f * (float)idx + 1.0f) - 1.0f) * 0.5f);
-        while (i * (i + 1) / 2 > idx) --i;
-        while ((i + 1) * (i + 2) / 2 <= idx) ++i;
-        const int j = idx - i * (i + 1) / 2;
-        const double v = joint_S_entry(in, i, j);
-        S[i * kJointLd + j] = v;
-        S[j * kJointLd + i] = v;
-        if (cov) {
-            cov[i * m + j] = v;
-            cov[j * m + i] = v;
-        }
-    }
+    double y = joint_assemble(a, h, lane, p0, m, S, Jl, om);
     if (!a.prefix && !a.joint) return;
     __syncthreads();
     double prev = 0.0, mine = joint_nan();

@@ -475,6 +475,7 @@ int bos_destroy(bos_solver* s) {
     bos::dev::associate_destroy(s->assoc);
     bos::dev::match_destroy(s->match);
     bos::dev::joint_destroy(s->joint);
+    bos::dev::jcbb_destroy(s->jcbb);
     if (s->rb) rocblas_destroy_handle(s->rb);
     if (s->comm) ncclCommDestroy(s->comm);
     for (hipEvent_t& e : s->ev)

@@ -21,6 +21,7 @@
 #include "../host/plan.hpp"
 #include "associate.hpp"
 #include "device_mem.hpp"
+#include "jcbb.hpp"
 #include "joint.hpp"
 #include "kernels.hpp"
 #include "lm.hpp"
@@ -212,6 +213,13 @@ struct bos_solver {
     std::vector<int32_t> joint_slot_of;
     double joint_ms[7] = {};
     int64_t joint_batch = 0;
+    // bos_jcbb (hip/jcbb.hpp): the batch's frames, tables and outputs, built at the first call (with pair_paths
+    // and the pair call's arena; joint_slot_of is shared); the last call's split in the joint call's slots and
+    // the nodes its search visited per frame; bos_debug_set_jcbb_batch's limit (0: the budgets alone)
+    bos::dev::Jcbb* jcbb = nullptr;
+    double jcbb_ms[7] = {};
+    std::vector<int64_t> jcbb_nodes;
+    int64_t jcbb_batch = 0;
     // ---- bos_cost / bos_optimize (hip/lm.hpp). The fp64 originals of what the cost pass reads and the
     // J+H keeps only in T: odometry z / information (upper triangle) and the bearing weights (has_w)
     std::vector<double> h_oz, h_oom, h_bw;

@@ -14,6 +14,7 @@
 #include "../../../include/bos_host.h"
 #include "associate.hpp"
 #include "match.hpp"
+#include "jcbb.hpp"
 #include "joint.hpp"
 #include "edge_cov.hpp"
 #include "node_cov.hpp"
@@ -783,6 +784,79 @@ int bos_plan_mf_joint_compatibility(const bos_problem* pb, const bos_options* op
         }
         s_done += B.s_count;
     }
+    return BOS_OK;
+}
+
+namespace {
+// One frame's result as the call returns it
+void jcbb_store(const bos::JcbbFrame& f, const bos::JcbbResult& r, int32_t* assignment, int32_t* n_paired, double* joint_nis,
+                double* prefix_nis, int32_t* complete, int64_t* nodes) {
+    for (int b = 0; b < f.m; ++b) {
+        if (assignment)
+            assignment[b] = r.choice[b] == bos::kJcbbNothing ? -1 : f.cand_landmark[f.cand_start[b] - f.cand_start[0] + r.choice[b]];
+        if (prefix_nis) prefix_nis[b] = r.prefix[b];
+    }
+    if (n_paired) *n_paired = r.n;
+    if (joint_nis) *joint_nis = r.nis;
+    if (complete) *complete = r.complete ? 1 : 0;
+    if (nodes) *nodes = r.nodes;
+}
+}  // namespace
+
+// Test hook: the serial search of csrc/host/jcbb.hpp on a given S_all and e_all.
+int bos_jcbb_search_host(int32_t m, const int32_t* cand_start, const int32_t* cand_landmark, const double* S_all, const double* e_all,
+                         const double* gate, int64_t max_nodes, int32_t no_bound, int32_t* assignment, int32_t* n_paired,
+                         double* joint_nis, double* prefix_nis, int32_t* complete, int64_t* nodes) {
+    if (m < 0 || m > bos::kJcbbMaxBearings) return hfail(BOS_ERR_INVALID, "bos_jcbb: a frame of more than BOS_JCBB_MAX_BEARINGS bearings");
+    if (const char* bad = bos::jcbb_bad_lists(INT32_MAX, m, cand_start, cand_landmark, gate, max_nodes))
+        return hfail(BOS_ERR_INVALID, std::string("bos_jcbb: ") + bad);
+    const int32_t P = cand_start[m];
+    if (P > bos::kJointMaxM) return hfail(BOS_ERR_INVALID, "bos_jcbb: a frame of more than BOS_JOINT_MAX_M pairings");
+    if (P > 0 && (!S_all || !e_all)) return hfail(BOS_ERR_INVALID, "bad argument");
+    bos::JcbbFrame f;
+    f.m = m; f.cand_start = cand_start; f.cand_landmark = cand_landmark; f.S = S_all; f.e = e_all; f.ld = P; f.gate = gate;
+    f.budget = bos::jcbb_budget(max_nodes); f.bound = !no_bound;
+    bos::JcbbResult r;
+    bos::jcbb_search(f, r);
+    jcbb_store(f, r, assignment, n_paired, joint_nis, prefix_nis, complete, nodes);
+    return BOS_OK;
+}
+
+// Test hook: bos_jcbb in its literal host form: the frames' all-pairings hypotheses through
+// bos_plan_mf_joint_compatibility, then the serial search per frame.
+int bos_plan_mf_jcbb(const bos_problem* pb, const bos_options* options, const double* vals, int32_t n_frames, const int32_t* frame_start,
+                     const int32_t* pose, const double* z, const double* omega, const int32_t* cand_start, const int32_t* cand_landmark,
+                     const double* gate, int64_t max_nodes, int64_t max_batch, int32_t* assignment, int32_t* n_paired, double* joint_nis,
+                     double* prefix_nis, int32_t* complete, double* innovation, double* innovation_cov, int64_t* nodes) {
+    if (!pb || !vals || !pb->pose_xyt || (!pb->landmark_xy && pb->num_landmarks > 0) || max_batch < 0)
+        return hfail(BOS_ERR_INVALID, "bad argument");
+    if (const char* bad = bos::jcbb_bad_argument(pb->num_poses, pb->num_landmarks, n_frames, frame_start, pose, z, omega, cand_start,
+                                                 cand_landmark, gate, max_nodes))
+        return hfail(BOS_ERR_INVALID, std::string("bos_jcbb: ") + bad);
+    if (n_frames == 0) return BOS_OK;
+    bos::JcbbPairings A;
+    bos::jcbb_pairings(n_frames, frame_start, pose, z, omega, cand_start, A);
+    const int32_t np = A.hyp_start[n_frames];
+    int64_t s_count = 0;
+    for (int32_t f = 0; f < n_frames; ++f) s_count += (int64_t)(A.hyp_start[f + 1] - A.hyp_start[f]) * (A.hyp_start[f + 1] - A.hyp_start[f]);
+    std::vector<double> e((size_t)np + 1), S((size_t)s_count + 1);
+    const int rc = bos_plan_mf_joint_compatibility(pb, options, vals, n_frames, A.hyp_start.data(), A.pose.data(), cand_landmark, A.z.data(),
+                                                   A.omega.data(), max_batch, nullptr, nullptr, e.data(), S.data());
+    if (rc) return rc;
+    int64_t s_off = 0;
+    for (int32_t fr = 0; fr < n_frames; ++fr) {
+        const int32_t b0 = frame_start[fr], p0 = A.hyp_start[fr], P = A.hyp_start[fr + 1] - p0;
+        bos::JcbbFrame f;
+        f.m = frame_start[fr + 1] - b0; f.cand_start = cand_start + b0; f.cand_landmark = cand_landmark + p0;
+        f.S = S.data() + s_off; f.e = e.data() + p0; f.ld = P; f.gate = gate; f.budget = bos::jcbb_budget(max_nodes);
+        bos::JcbbResult r;
+        bos::jcbb_search(f, r);
+        jcbb_store(f, r, assignment ? assignment + b0 : nullptr, n_paired ? n_paired + fr : nullptr, joint_nis ? joint_nis + fr : nullptr,
+                   prefix_nis ? prefix_nis + b0 : nullptr, complete ? complete + fr : nullptr, nodes ? nodes + fr : nullptr);
+        s_off += (int64_t)P * P;
+    }
+    if (innovation) std::copy(e.begin(), e.begin() + np, innovation);
+    if (innovation_cov) std::copy(S.begin(), S.begin() + s_count, innovation_cov);
     return BOS_OK;
 }
 
