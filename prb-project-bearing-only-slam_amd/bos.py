@@ -1390,15 +1390,19 @@ class Solver:
         out["solver_info"] = info.value
         return out
 
+    def _timing(self, fn: str, slots: tuple, bytes_key: str, *more) -> dict:
+        """A covariance call's timing getter `fn`(handle, ms, bytes, *more): its ms slots under the names
+        `slots`, in order, then the device bytes under `bytes_key`."""
+        ms = np.zeros(len(slots))
+        nb = ctypes.c_int64(0)
+        _check(getattr(lib(), fn)(self._h, _ptr(ms, ctypes.c_double), ctypes.byref(nb), *more), fn)
+        return {**dict(zip(slots, ms)), bytes_key: nb.value}
+
     def edge_covariances_timing(self) -> dict:
         """The last edge_covariances() call's split in ms and the feature's device bytes
         (bos_edge_covariances_timing)."""
-        ms = np.zeros(5)
-        nb = ctypes.c_int64(0)
-        _check(lib().bos_edge_covariances_timing(self._h, _ptr(ms, ctypes.c_double), ctypes.byref(nb)),
-               "bos_edge_covariances_timing")
-        return {"jh_ms": ms[0], "factor_ms": ms[1], "selinv_ms": ms[2], "project_ms": ms[3], "download_ms": ms[4],
-                "edge_bytes": nb.value}
+        return self._timing("bos_edge_covariances_timing", ("jh_ms", "factor_ms", "selinv_ms", "project_ms", "download_ms"),
+                            "edge_bytes")
 
     def pair_covariances(self, node_a, node_b, cross: bool = True, projected: bool = True, blocks: bool = True) -> dict:
         """Joint covariances of arbitrary node pairs at the current estimate (bos_pair_covariances). Node
@@ -1416,12 +1420,8 @@ class Solver:
     def pair_covariances_timing(self) -> dict:
         """The last pair_covariances() call's split in ms and the feature's device bytes
         (bos_pair_covariances_timing)."""
-        ms = np.zeros(6)
-        nb = ctypes.c_int64(0)
-        _check(lib().bos_pair_covariances_timing(self._h, _ptr(ms, ctypes.c_double), ctypes.byref(nb)),
-               "bos_pair_covariances_timing")
-        return {"prepare_ms": ms[0], "jh_ms": ms[1], "factor_ms": ms[2], "path_ms": ms[3], "product_ms": ms[4],
-                "download_ms": ms[5], "pair_bytes": nb.value}
+        return self._timing("bos_pair_covariances_timing",
+                            ("prepare_ms", "jh_ms", "factor_ms", "path_ms", "product_ms", "download_ms"), "pair_bytes")
 
     def node_covariances(self, nodes, cross: bool = True, projected: bool = True, marginals: bool = False) -> dict:
         """One node's covariance against every node, for each node of `nodes`, at the current estimate
@@ -1441,12 +1441,8 @@ class Solver:
     def node_covariances_timing(self) -> dict:
         """The last node_covariances() call's split in ms and the feature's device bytes
         (bos_node_covariances_timing)."""
-        ms = np.zeros(7)
-        nb = ctypes.c_int64(0)
-        _check(lib().bos_node_covariances_timing(self._h, _ptr(ms, ctypes.c_double), ctypes.byref(nb)),
-               "bos_node_covariances_timing")
-        return {"prepare_ms": ms[0], "jh_ms": ms[1], "factor_ms": ms[2], "selinv_ms": ms[3], "column_ms": ms[4],
-                "gather_ms": ms[5], "download_ms": ms[6], "node_bytes": nb.value}
+        return self._timing("bos_node_covariances_timing",
+                            ("prepare_ms", "jh_ms", "factor_ms", "selinv_ms", "column_ms", "gather_ms", "download_ms"), "node_bytes")
 
     def associate_bearings(self, pose, z, omega=None, gate: float = np.inf, k: int = 4, nis_all: bool = False) -> dict:
         """Gates new bearings against every landmark at the current estimate (bos_associate_bearings):
@@ -1466,12 +1462,9 @@ class Solver:
     def associate_bearings_timing(self) -> dict:
         """The last associate_bearings() call's split in ms and the feature's device bytes
         (bos_associate_bearings_timing)."""
-        ms = np.zeros(8)
-        nb = ctypes.c_int64(0)
-        _check(lib().bos_associate_bearings_timing(self._h, _ptr(ms, ctypes.c_double), ctypes.byref(nb)),
-               "bos_associate_bearings_timing")
-        return {"prepare_ms": ms[0], "jh_ms": ms[1], "factor_ms": ms[2], "selinv_ms": ms[3], "column_ms": ms[4],
-                "nis_ms": ms[5], "select_ms": ms[6], "download_ms": ms[7], "assoc_bytes": nb.value}
+        return self._timing("bos_associate_bearings_timing",
+                            ("prepare_ms", "jh_ms", "factor_ms", "selinv_ms", "column_ms", "nis_ms", "select_ms", "download_ms"),
+                            "assoc_bytes")
 
     def debug_set_associate_chunk(self, max_bearings: int):
         """Test knob (bos_debug_set_associate_chunk): associate_bearings() closes a chunk at this many
@@ -1499,12 +1492,8 @@ class Solver:
     def joint_compatibility_timing(self) -> dict:
         """The last joint_compatibility() call's split in ms and the device bytes it uses
         (bos_joint_compatibility_timing)."""
-        ms = np.zeros(7)
-        nb = ctypes.c_int64(0)
-        _check(lib().bos_joint_compatibility_timing(self._h, _ptr(ms, ctypes.c_double), ctypes.byref(nb)),
-               "bos_joint_compatibility_timing")
-        return {"prepare_ms": ms[0], "jh_ms": ms[1], "factor_ms": ms[2], "path_ms": ms[3], "product_ms": ms[4],
-                "nis_ms": ms[5], "download_ms": ms[6], "joint_bytes": nb.value}
+        return self._timing("bos_joint_compatibility_timing",
+                            ("prepare_ms", "jh_ms", "factor_ms", "path_ms", "product_ms", "nis_ms", "download_ms"), "joint_bytes")
 
     def debug_set_joint_batch(self, max_hypotheses: int):
         """Test knob (bos_debug_set_joint_batch): joint_compatibility() closes a batch at this many
@@ -1535,15 +1524,13 @@ class Solver:
     def jcbb_timing(self) -> dict:
         """The last jcbb() call's split in ms, the device bytes it uses and the nodes its search visited per
         frame (bos_jcbb_timing)."""
-        ms = np.zeros(7)
-        nb, nf = ctypes.c_int64(0), ctypes.c_int32(0)
-        _check(lib().bos_jcbb_timing(self._h, _ptr(ms, ctypes.c_double), ctypes.byref(nb), 0, None, ctypes.byref(nf)),
-               "bos_jcbb_timing")
+        slots = ("prepare_ms", "jh_ms", "factor_ms", "path_ms", "product_ms", "search_ms", "download_ms")
+        nf = ctypes.c_int32(0)
+        self._timing("bos_jcbb_timing", slots, "jcbb_bytes", 0, None, ctypes.byref(nf))
         nodes = np.zeros(max(nf.value, 1), dtype=np.int64)
-        _check(lib().bos_jcbb_timing(self._h, _ptr(ms, ctypes.c_double), ctypes.byref(nb), nf.value, _ptr(nodes, ctypes.c_int64),
-                                     None), "bos_jcbb_timing")
-        return {"prepare_ms": ms[0], "jh_ms": ms[1], "factor_ms": ms[2], "path_ms": ms[3], "product_ms": ms[4],
-                "search_ms": ms[5], "download_ms": ms[6], "jcbb_bytes": nb.value, "nodes": nodes[:nf.value]}
+        out = self._timing("bos_jcbb_timing", slots, "jcbb_bytes", nf.value, _ptr(nodes, ctypes.c_int64), None)
+        out["nodes"] = nodes[:nf.value]
+        return out
 
     def debug_set_jcbb_batch(self, max_frames: int):
         """Test knob (bos_debug_set_jcbb_batch): jcbb() closes a batch at this many frames; 0 restores the
@@ -1583,11 +1570,9 @@ class Solver:
     def match_timing(self) -> dict:
         """The split in ms of the last match_landmarks() or match_poses() call and the feature's device
         bytes (bos_match_timing)."""
-        ms = np.zeros(8)
-        nb = ctypes.c_int64(0)
-        _check(lib().bos_match_timing(self._h, _ptr(ms, ctypes.c_double), ctypes.byref(nb)), "bos_match_timing")
-        return {"prepare_ms": ms[0], "jh_ms": ms[1], "factor_ms": ms[2], "selinv_ms": ms[3], "column_ms": ms[4],
-                "score_ms": ms[5], "select_ms": ms[6], "download_ms": ms[7], "match_bytes": nb.value}
+        return self._timing("bos_match_timing",
+                            ("prepare_ms", "jh_ms", "factor_ms", "selinv_ms", "column_ms", "score_ms", "select_ms", "download_ms"),
+                            "match_bytes")
 
     def debug_set_match_chunk(self, max_rows: int):
         """Test knob (bos_debug_set_match_chunk): match_poses() closes a chunk at this many measurements
@@ -1618,10 +1603,7 @@ class Solver:
 
     def marginals_timing(self) -> dict:
         """The last marginals() call's split in ms and the Sigma-front buffer's bytes (bos_marginals_timing)."""
-        ms = np.zeros(4)
-        nb = ctypes.c_int64(0)
-        _check(lib().bos_marginals_timing(self._h, _ptr(ms, ctypes.c_double), ctypes.byref(nb)), "bos_marginals_timing")
-        return {"jh_ms": ms[0], "factor_ms": ms[1], "selinv_ms": ms[2], "download_ms": ms[3], "sigma_bytes": nb.value}
+        return self._timing("bos_marginals_timing", ("jh_ms", "factor_ms", "selinv_ms", "download_ms"), "sigma_bytes")
 
     def get_state(self):
         pose = np.zeros((self.P.NP, 3))

@@ -1,8 +1,10 @@
 // The C ABI handle (include/bos.h) and what its implementation files share: solver_create.hip (plan,
 // uploads, bos_create / bos_destroy), solver_step.hip (the GN step, its graphs and the step's entry
-// points), solver_shard.hip (the multi-rank phases and exchanges), solver_cov.hip (marginals, edge,
-// pair and node covariances, bearing association, node matching, joint compatibility) and solver_lm.hip (bos_cost / bos_optimize). The handle owns every device buffer
-// (mem), the static plan (host/plan.hpp), the rocSOLVER refactorization state and the RCCL communicator.
+// points), solver_shard.hip (the multi-rank phases and exchanges), solver_lm.hip (bos_cost / bos_optimize)
+// and the covariance calls, which share cov_call.hpp: solver_cov.hip (marginals and edge covariances),
+// solver_cov_pair.hip (pair covariances, joint compatibility, JCBB) and solver_cov_node.hip (node covariances,
+// bearing association, node matching). The handle owns every device buffer (mem), the static plan
+// (host/plan.hpp), the rocSOLVER refactorization state and the RCCL communicator.
 #pragma once
 
 #include <hip/hip_runtime.h>
