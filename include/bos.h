@@ -626,6 +626,82 @@ int bos_jcbb(struct bos_solver* s, int32_t n_frames, const int32_t* frame_start,
              const double* omega, const int32_t* cand_start, const int32_t* cand_landmark, const double* gate, int64_t max_nodes,
              int32_t* assignment, int32_t* n_paired, double* joint_nis, double* prefix_nis, int32_t* complete, double* innovation,
              double* innovation_cov, int32_t* solver_info);
+/* Edge consistency at the current estimate (Baarda's data snooping): every bearing and odometry edge that IS
+ * in the graph is tested against the estimate it helped to produce, and the k worst of each kind are listed on
+ * the device. H is sum J^T Omega J + lambda I and the robust kernel scales the right-hand side only, so with
+ * R = Omega^-1 and P = J Sigma_joint J^T (bos_edge_covariances' bearing_var / odom_cov) the residual of an edge
+ * at the optimum has the covariance T = R - P, positive semi-definite in exact arithmetic for every
+ * lambda >= 0. Per edge:
+ *   w2         = e^T T^-1 e, the normalised residual squared: chi^2 with 1 (bearing) or 3 (odometry) degrees of
+ *                freedom for a consistent edge
+ *   chi2       = e^T Omega e, the edge's term of bos_step_stats.chi2
+ *   redundancy = 1 - tr(Omega P) / d, d = 1 or 3; over all edges sum tr(Omega P) = n - lambda tr(Sigma), n of
+ *                bos_system_info and the trace over the blocks of bos_marginals
+ * Bearing edge i (pose p, landmark l, information omega, 1 where the problem gave none), every line one IEEE
+ * operation at a time, without FP contraction:
+ *   e    = bearing_error<double> (csrc/host/bos_math.hpp) at the fp64 master state with cos / sin computed in
+ *          fp64, on every handle, fp32 ones included (as bos_cost and bos_associate_bearings)
+ *   chi2 = (e * omega) * e
+ *   var  = bit for bit the bearing_var[i] bos_edge_covariances returns at this state, with its fixed-pose rule
+ *          (the same kernel's output, read in place)
+ *   R = 1.0 / omega,  T = R - var,  w2 = (e * e) / T, NaN when T is not finite and > 0
+ *   redundancy = 1.0 - omega * var
+ * Odometry edge j (Omega is read as bos_create keeps it: the upper triangle u = (00, 01, 02, 11, 12, 22) of
+ * odom_omega[j], mirrored):
+ *   e    = the error of odometry_error_jacobian<double> at the fp64 master state, fp64 cos / sin
+ *   chi2 = (e0 * Oe0 + e1 * Oe1) + e2 * Oe2 with Oe0 = (u00 * e0 + u01 * e1) + u02 * e2, Oe1 = (u01 * e0 +
+ *          u11 * e1) + u12 * e2, Oe2 = (u02 * e0 + u12 * e1) + u22 * e2: the order of bos_cost's pass
+ *   P    = bit for bit odom_cov[j] of bos_edge_covariances at this state, read in place
+ *   R    = Omega^-1, formed once per edge on the host at the feature's first call by the code of
+ *          bos_match_information_inverse (bos_host.h); an Omega it refuses (not finite, a pivot of its LDL^T not
+ *          positive) gives an R of NaNs, hence w2 NaN
+ *   T    = R - P entry-wise on the lower triangle
+ *   w2   = e^T T^-1 e through the LDL^T of T: exactly the sequence written out for bos_match_poses with T in
+ *          the place of S (the same function, csrc/host/match.hpp match_pose_nis); NaN when a pivot is not finite
+ *          and > 0
+ *   redundancy = 1.0 - t / 3.0, t the sum of Omega_ab * P_ab over a, b in row-major order, starting from 0.0
+ * An odometry self-loop (src == dst) contributes nothing to H: its w2 and redundancy are NaN by definition, its
+ * chi2 is evaluated like every other edge's.
+ * Lists, per kind, k in 1 .. BOS_EDGE_CHECK_MAX_K: the min(k, n_over) LARGEST w2 among the edges whose w2 is
+ * finite and >= the kind's gate, descending by w2, equal w2 to the lower edge index first; n_over counts all
+ * edges that qualify, not min(., k). A gate is finite and >= 0; 0 lists every finite score.
+ * Outputs (host pointers; any may be NULL: it is neither computed nor downloaded; edge = measurement order):
+ *   cand_bearing            [k]     bearing index, -1 where nothing is listed
+ *   cand_bearing_w2         [k]     -inf where nothing is listed; bit for bit bearing_w2[cand_bearing[j]]
+ *   cand_bearing_innovation [k]     e of the listed bearing, 0 where nothing is listed
+ *   cand_bearing_resvar     [k]     T of the listed bearing, 0 where nothing is listed
+ *   n_over_bearing          [1]
+ *   cand_odom, cand_odom_w2 [k]     likewise, indices among the odometry edges
+ *   cand_odom_innovation    [k][3]  e
+ *   cand_odom_rescov        [k][9]  T, row-major, its lower triangle mirrored
+ *   n_over_odom             [1]
+ *   bearing_w2, bearing_chi2, bearing_redundancy  [M_b]  the whole rows
+ *   odom_w2, odom_chi2, odom_redundancy           [M_o]
+ * A caller reproduces a listed w2 from the listed e and T with IEEE arithmetic.
+ * BOS_ERR_INVALID, with nothing touched, for a gate that is NaN, negative or infinite and for k outside
+ * 1 .. BOS_EDGE_CHECK_MAX_K. A kind without edges (M_b == 0 or M_o == 0) has lists of padding and a count of 0.
+ * On a handle whose only node is the fixed pose (no landmark, hence no bearing, and every odometry edge a
+ * self-loop) P is zero everywhere: the lists are padding, the counts 0, w2 and redundancy NaN, and chi2 is
+ * evaluated on the host by the same code; *solver_info is 0.
+ * One pass: the selected inverse with the cross blocks' emission and the projection kernel of
+ * bos_edge_covariances into its buffers, one kernel with a thread per edge that reads bearing_var / odom_cov
+ * in place and the fp64 measurements of bos_cost, then per kind the two selection launches of
+ * bos_associate_bearings over the row of -w2. By default the lists alone are downloaded (1 872 bytes).
+ * Exact rules: two calls give identical bits; duplicate edges of one orientation return identical bits; a
+ * self-loop is never listed and never counted.
+ * H_nf, the damping, the kernel threshold, the state handling, the synchronous behaviour, *solver_info, the
+ * clearing of the pivot word, the "counts as a bos_linearize" rule and bos_get_last_dx afterwards are exactly
+ * those of bos_edge_covariances. BOS_ERR_SOLVER on a stalled factorization; BOS_ERR_UNSUPPORTED and
+ * BOS_ERR_DEVICE fire on exactly the conditions of bos_edge_covariances: the handle stays usable. The buffers
+ * (with those of bos_edge_covariances and of bos_cost, if they have not run) are allocated at the first call
+ * that asks for an output; a handle that never calls pays nothing. */
+#define BOS_EDGE_CHECK_MAX_K BOS_ASSOC_MAX_K
+int bos_edge_consistency(struct bos_solver* s, double gate_bearing, double gate_odom, int32_t k, int32_t* cand_bearing,
+                         double* cand_bearing_w2, double* cand_bearing_innovation, double* cand_bearing_resvar,
+                         int32_t* n_over_bearing, int32_t* cand_odom, double* cand_odom_w2, double* cand_odom_innovation,
+                         double* cand_odom_rescov, int32_t* n_over_odom, double* bearing_w2, double* bearing_chi2,
+                         double* bearing_redundancy, double* odom_w2, double* odom_chi2, double* odom_redundancy,
+                         int32_t* solver_info);
 /*
  * Levenberg-Marquardt with on-device step control (DESIGN.md §4 "Levenberg-Marquardt"). The objective is
  *   F(x) = sum over all edges of h(rho), rho = e^T Omega e, h(rho) = rho for rho <= kt and

@@ -115,6 +115,19 @@ int bos_plan_mf_edge_covariances(const bos_problem* problem, const bos_options* 
                                  double* bearing_cross, double* odom_cross, double* bearing_var, double* odom_cov,
                                  double* pose_cov, double* landmark_cov);
 
+/* Test hook: what bos_edge_consistency computes, in its literal host form: bearing_var / odom_cov of
+ * bos_plan_mf_edge_covariances (the host selected inverse and the plan's cross records), then e, T, w2, chi2
+ * and the redundancy of every edge by the code the device kernel runs (csrc/host/edge_check.hpp), at the
+ * problem's state, Omega read by its upper triangle as bos_create keeps it, and the lists by a plain stable
+ * sort (descending w2, equal w2 to the lower edge first). Arguments, outputs and rules as for
+ * bos_edge_consistency (without solver_info); any output may be NULL. No device is used. */
+int bos_plan_mf_edge_consistency(const bos_problem* problem, const bos_options* options, const double* vals, double gate_bearing,
+                                 double gate_odom, int32_t k, int32_t* cand_bearing, double* cand_bearing_w2,
+                                 double* cand_bearing_innovation, double* cand_bearing_resvar, int32_t* n_over_bearing,
+                                 int32_t* cand_odom, double* cand_odom_w2, double* cand_odom_innovation, double* cand_odom_rescov,
+                                 int32_t* n_over_odom, double* bearing_w2, double* bearing_chi2, double* bearing_redundancy,
+                                 double* odom_w2, double* odom_chi2, double* odom_redundancy);
+
 /* Test hook: what bos_pair_covariances computes, in its literal host form over the host factorization of
  * H_nf (vals as for bos_plan_mf_marginals): the same root-path walk per distinct node, the products
  * summed in row order, and the projection by the code the device kernel runs (csrc/host/pair_cov.hpp,
@@ -275,6 +288,12 @@ int bos_marginals_timing(const struct bos_solver* s, double ms[4], int64_t* sigm
  * events) and download of the outputs (host clock); *edge_bytes (may be NULL) = bytes of the feature's
  * device buffers (0 before the first call). */
 int bos_edge_covariances_timing(const struct bos_solver* s, double ms[5], int64_t* edge_bytes);
+/* Measurement helper (tools/edge_consistency_time.py): the last bos_edge_consistency call's split, ms[7] = host
+ * preparation (host clock; R and the arena at the first call), J+H build, factorization, selected inverse with
+ * the cross blocks' emission, projection + scoring kernels, the selections (HIP events) and download of the
+ * outputs (host clock); *bytes (may be NULL) = bytes of the feature's own arena (0 before the first call; the
+ * edge call's buffers, which it reads, are bos_edge_covariances_timing's). */
+int bos_edge_consistency_timing(const struct bos_solver* s, double ms[7], int64_t* bytes);
 /* Measurement helper (tools/pair_cov_time.py): the last bos_pair_covariances call's split, ms[6] = host
  * preparation and upload (host clock), J+H build, factorization, path solve, product and projection (HIP
  * events, summed over the call's batches) and download of the outputs (host clock); *bytes (may be NULL)

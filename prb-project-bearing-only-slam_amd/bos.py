@@ -59,6 +59,7 @@ EXPORTED_SYMBOLS = [
     "bos_lm_default_options", "bos_cost", "bos_optimize", "bos_time_cost", "bos_cpu_gn_set_kernel_threshold",
     "bos_cpu_gn_cost", "bos_cpu_gn_optimize", "bos_lm_rule_apply",
     "bos_edge_covariances", "bos_plan_mf_edge_covariances", "bos_edge_covariances_timing",
+    "bos_edge_consistency", "bos_plan_mf_edge_consistency", "bos_edge_consistency_timing",
     "bos_pair_covariances", "bos_plan_mf_pair_covariances", "bos_plan_pair_paths", "bos_pair_covariances_timing",
     "bos_debug_set_pair_batch",
     "bos_node_covariances", "bos_plan_mf_node_covariances", "bos_node_covariances_timing",
@@ -79,6 +80,8 @@ P2P_HANDLE_BYTES = 64   # include/bos.h BOS_P2P_HANDLE_BYTES
 
 _dp = ctypes.POINTER(ctypes.c_double)
 _ip = ctypes.POINTER(ctypes.c_int32)
+# the outputs of bos_edge_consistency: per kind the lists and the count, then the rows of both kinds
+_EDGE_CHECK_SIG = [_ip, _dp, _dp, _dp, _ip] * 2 + [_dp] * 6
 
 
 class BosError(RuntimeError):
@@ -222,6 +225,10 @@ def lib():
         "bos_plan_mf_edge_covariances": (ctypes.c_int, [ctypes.POINTER(bos_problem), ctypes.POINTER(bos_options), _dp, _dp, _dp,
                                                          _dp, _dp, _dp, _dp]),
         "bos_edge_covariances_timing": (ctypes.c_int, [vp, _dp, ctypes.POINTER(ctypes.c_int64)]),
+        "bos_edge_consistency": (ctypes.c_int, [vp, ctypes.c_double, ctypes.c_double, ctypes.c_int32, *_EDGE_CHECK_SIG, _ip]),
+        "bos_plan_mf_edge_consistency": (ctypes.c_int, [ctypes.POINTER(bos_problem), ctypes.POINTER(bos_options), _dp, ctypes.c_double,
+                                                         ctypes.c_double, ctypes.c_int32, *_EDGE_CHECK_SIG]),
+        "bos_edge_consistency_timing": (ctypes.c_int, [vp, _dp, ctypes.POINTER(ctypes.c_int64)]),
         "bos_marginals_timing": (ctypes.c_int, [vp, _dp, ctypes.POINTER(ctypes.c_int64)]),
         "bos_pair_covariances": (ctypes.c_int, [vp, ctypes.c_int64, _ip, _ip, _dp, _dp, _dp, _dp, _ip]),
         "bos_plan_mf_pair_covariances": (ctypes.c_int, [ctypes.POINTER(bos_problem), ctypes.POINTER(bos_options), _dp,
@@ -579,6 +586,56 @@ def plan_mf_edge_covariances(P: Problem, vals, solver: int = BOS_SOLVER_SCHUR, s
                                               *[_ptr(out[k], ctypes.c_double) for k in _EDGE_COV_ORDER]),
            "plan_mf_edge_covariances")
     return out
+
+
+EDGE_CHECK_MAX_K = 8   # include/bos.h BOS_EDGE_CHECK_MAX_K
+# bytes of one kind's lists as a call downloads them: sizeof(bos::dev::EdgeCheckLists), pinned by a static_assert in
+# csrc/hip/edge_check.hpp
+EDGE_CHECK_LIST_BYTES = 936
+_EDGE_CHECK_ORDER = ("cand_bearing", "cand_bearing_w2", "cand_bearing_innovation", "cand_bearing_resvar", "n_over_bearing",
+                     "cand_odom", "cand_odom_w2", "cand_odom_innovation", "cand_odom_rescov", "n_over_odom",
+                     "bearing_w2", "bearing_chi2", "bearing_redundancy", "odom_w2", "odom_chi2", "odom_redundancy")
+
+
+def _edge_check_arrays(P: Problem, k: int, lists: bool, rows: bool, kinds=("bearing", "odom")) -> dict:
+    """The output arrays of an edge-consistency call in the C argument order; None where not asked for."""
+    Mb, Mo, k = len(P.b_z), len(P.o_z), max(int(k), 0)
+    b, o = "bearing" in kinds, "odom" in kinds
+    shape = {"cand_bearing": (k,), "cand_bearing_w2": (k,), "cand_bearing_innovation": (k,), "cand_bearing_resvar": (k,),
+             "n_over_bearing": (1,), "cand_odom": (k,), "cand_odom_w2": (k,), "cand_odom_innovation": (k, 3),
+             "cand_odom_rescov": (k, 3, 3), "n_over_odom": (1,), "bearing_w2": (Mb,), "bearing_chi2": (Mb,),
+             "bearing_redundancy": (Mb,), "odom_w2": (Mo,), "odom_chi2": (Mo,), "odom_redundancy": (Mo,)}
+    out = {}
+    for key in _EDGE_CHECK_ORDER:
+        want = (b if "bearing" in key else o) and (lists if key.startswith(("cand_", "n_over_")) else rows)
+        integer = key.startswith("n_over_") or key in ("cand_bearing", "cand_odom")
+        out[key] = np.zeros(shape[key], dtype=np.int32 if integer else np.float64) if want else None
+    return out
+
+
+def _edge_check_pointers(out: dict) -> list:
+    return [_ptr(out[key], ctypes.c_int32 if out[key] is not None and out[key].dtype == np.int32 else ctypes.c_double)
+            for key in _EDGE_CHECK_ORDER]
+
+
+def _edge_check_result(out: dict) -> dict:
+    for key in ("n_over_bearing", "n_over_odom"):
+        out[key] = None if out[key] is None else int(out[key][0])
+    return out
+
+
+def plan_mf_edge_consistency(P: Problem, vals, gate_bearing: float = 0.0, gate_odom: float = 0.0, k: int = 4, rows: bool = True,
+                             solver: int = BOS_SOLVER_SCHUR, schur_leaf: int = 0) -> dict:
+    """Host form of Solver.edge_consistency() (test hook, bos_plan_mf_edge_consistency): the host selected inverse
+    of the H_nf whose stored entries are vals, then every edge's e, T, w2, chi2 and redundancy at P's state and a
+    plain stable sort. Returns the dict of arrays (no solver_info)."""
+    cs = P.c_struct()
+    v = np.ascontiguousarray(vals, dtype=np.float64)
+    out = _edge_check_arrays(P, k, True, rows)
+    opt = options(solver, schur_leaf=schur_leaf)
+    _check(lib().bos_plan_mf_edge_consistency(ctypes.byref(cs), ctypes.byref(opt), _ptr(v, ctypes.c_double), gate_bearing, gate_odom, k,
+                                              *_edge_check_pointers(out)), "plan_mf_edge_consistency")
+    return _edge_check_result(out)
 
 
 _PAIR_COV_ORDER = ("cross", "projected", "cov_a", "cov_b")
@@ -1403,6 +1460,28 @@ class Solver:
         (bos_edge_covariances_timing)."""
         return self._timing("bos_edge_covariances_timing", ("jh_ms", "factor_ms", "selinv_ms", "project_ms", "download_ms"),
                             "edge_bytes")
+
+    def edge_consistency(self, gate_bearing: float = 0.0, gate_odom: float = 0.0, k: int = 4, rows: bool = False, lists: bool = True,
+                         kinds=("bearing", "odom")) -> dict:
+        """Tests the edges that are in the graph against the current estimate (bos_edge_consistency): per kind
+        the k largest normalised residuals w2 = e^T (Omega^-1 - J Sigma J^T)^-1 e at or above the gate,
+        descending: cand_bearing / cand_odom [k] (edge index, -1 padding), cand_*_w2 [k] (-inf padding),
+        cand_bearing_innovation / _resvar [k], cand_odom_innovation [k, 3], cand_odom_rescov [k, 3, 3] and the
+        counts n_over_*; with rows the whole bearing_/odom_ w2, chi2 and redundancy arrays. Outputs not asked
+        for (rows, lists, a kind not in kinds) are None. Includes solver_info."""
+        out = _edge_check_arrays(self.P, k, lists, rows, kinds)
+        info = ctypes.c_int32(0)
+        _check(lib().bos_edge_consistency(self._h, gate_bearing, gate_odom, k, *_edge_check_pointers(out), ctypes.byref(info)),
+               "bos_edge_consistency")
+        out = _edge_check_result(out)
+        out["solver_info"] = info.value
+        return out
+
+    def edge_consistency_timing(self) -> dict:
+        """The last edge_consistency() call's split in ms and the feature's device bytes
+        (bos_edge_consistency_timing)."""
+        return self._timing("bos_edge_consistency_timing", ("host_ms", "jh_ms", "factor_ms", "selinv_ms", "score_ms", "select_ms",
+                                                            "download_ms"), "bytes")
 
     def pair_covariances(self, node_a, node_b, cross: bool = True, projected: bool = True, blocks: bool = True) -> dict:
         """Joint covariances of arbitrary node pairs at the current estimate (bos_pair_covariances). Node

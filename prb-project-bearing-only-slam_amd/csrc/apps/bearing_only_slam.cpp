@@ -1,8 +1,10 @@
 // Headless drop-in for executables/bearing_only_slam.cpp (reference :40-116).
 // Usage: bearing_only_slam <dataset_fname> [--iters N] [--lm] [--fp32] [--dense|--schur] [--dump out.g2o]
-//                          [--ppm out.ppm] [--quiet]
+//                          [--ppm out.ppm] [--check-edges K] [--quiet]
 // --lm: Levenberg-Marquardt (bos_optimize, at most --iters iterations, it stops by itself) instead of
 // the fixed count of Gauss-Newton steps; one line per iteration.
+// --check-edges K: after the run, the K (1 .. 8) bearings and odometry edges with the largest normalised residual
+// (bos_edge_consistency): edge index, node ids, e, w2 and the redundancy number, one line per edge.
 // Same flow as the reference's main: parse_g2o, default the fixed pose, triangulate the
 // landmarks, construct the Solver, then iterate (the reference's Tab press = 50 iterations,
 // :93-99). The OpenCV window is replaced by a per-iteration chi^2 line, an optional g2o dump and
@@ -25,11 +27,11 @@ using namespace proj02;
 int main(int argc, char** argv) {
     if (argc < 2) {
         std::cout << "usage: bearing_only_slam <dataset_fname> [--iters N] [--lm] [--fp32] [--dense|--schur] [--dump out.g2o] "
-                     "[--ppm out.ppm] [--quiet]"
+                     "[--ppm out.ppm] [--check-edges K] [--quiet]"
                   << std::endl;
         return 1;
     }
-    int iters = 50;
+    int iters = 50, check_edges = 0;
     bool quiet = false, lm = false;
     std::string dump, ppm;
     bos_options opt;
@@ -42,6 +44,7 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--schur")) opt.solver = BOS_SOLVER_SCHUR;
         else if (!std::strcmp(argv[i], "--dump") && i + 1 < argc) dump = argv[++i];
         else if (!std::strcmp(argv[i], "--ppm") && i + 1 < argc) ppm = argv[++i];
+        else if (!std::strcmp(argv[i], "--check-edges") && i + 1 < argc) check_edges = std::atoi(argv[++i]);
         else if (!std::strcmp(argv[i], "--quiet")) quiet = true;
         else { std::cerr << "unknown argument " << argv[i] << std::endl; return 1; }
     }
@@ -88,6 +91,24 @@ int main(int argc, char** argv) {
             if (!quiet)
                 std::printf("iter %3d  chi2 %.9g  robust %d  max|dx| %.3g  J+H %.3f ms  solve %.3f ms\n", it, s.chi2,
                             s.n_robust, s.max_abs_dx, s.t_linearize_ms, s.t_solve_ms);
+        }
+        if (check_edges != 0) {
+            const int k = check_edges;
+            std::vector<int32_t> cb(8, -1), co(8, -1);
+            std::vector<double> cbw(8), cbe(8), cow(8), coe(24), rb(bearings.size()), ro(odometries.size());
+            int32_t nb = 0, no = 0;
+            if (bos_edge_consistency(solver.handle(), 0.0, 0.0, k, cb.data(), cbw.data(), cbe.data(), nullptr, &nb, co.data(), cow.data(),
+                                     coe.data(), nullptr, &no, nullptr, nullptr, rb.data(), nullptr, nullptr, ro.data(), nullptr) != BOS_OK)
+                throw std::runtime_error(bos_last_error());
+            std::printf("worst bearings (of %d with a finite w2):\n", nb);
+            for (int j = 0; j < k && cb[j] >= 0; ++j)
+                std::printf("  bearing %d  pose %d  landmark %d  e %.6g  w2 %.6g  redundancy %.6g\n", cb[j], bearings[cb[j]].get_pose_id(),
+                            bearings[cb[j]].get_lm_id(), cbe[j], cbw[j], rb[cb[j]]);
+            std::printf("worst odometry edges (of %d with a finite w2):\n", no);
+            for (int j = 0; j < k && co[j] >= 0; ++j)
+                std::printf("  odometry %d  pose %d  pose %d  e (%.6g, %.6g, %.6g)  w2 %.6g  redundancy %.6g\n", co[j],
+                            odometries[co[j]].get_source_id(), odometries[co[j]].get_dest_id(), coe[3 * j], coe[3 * j + 1], coe[3 * j + 2],
+                            cow[j], ro[co[j]]);
         }
         if (!ppm.empty()) render(solver.state, ppm);
         if (!dump.empty() && write_g2o(dump, solver.state, bearings, odometries, fixed_pose_id, true)) {

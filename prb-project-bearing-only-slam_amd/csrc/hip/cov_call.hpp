@@ -51,8 +51,9 @@ struct CovCall {
     // the word read and cleared and the stream drained; fails on kMfStall, with *solver_info left 0
     int factor();
     // the marginals' own pass on this factorization, between events 2 and 3, to slot 3: *sig is Sigma's
-    // diagonal blocks (device, [9 NP | 4 NL])
-    int selected_inverse(const double** sig);
+    // diagonal blocks (device, [9 NP | 4 NL]); emit_cross: the edges' cross blocks into the pair buffer as well
+    // (after edge_cov_setup), as bos_edge_covariances' pass runs it
+    int selected_inverse(const double** sig, bool emit_cross = false);
     // event ev recorded and the stream drained, then the device layers' code of what was enqueued (dev_fail)
     int drain(int ev, int prc, const std::string& err);
     void host_ms(int slot, Clock::time_point t0) { ms[slot] += ms_since(t0); }

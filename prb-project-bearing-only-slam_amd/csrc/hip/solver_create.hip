@@ -476,6 +476,7 @@ int bos_destroy(bos_solver* s) {
     bos::dev::match_destroy(s->match);
     bos::dev::joint_destroy(s->joint);
     bos::dev::jcbb_destroy(s->jcbb);
+    bos::dev::edge_check_destroy(s->edge_check);
     if (s->rb) rocblas_destroy_handle(s->rb);
     if (s->comm) ncclCommDestroy(s->comm);
     for (hipEvent_t& e : s->ev)

@@ -1,7 +1,7 @@
 // The C ABI handle (include/bos.h) and what its implementation files share: solver_create.hip (plan,
 // uploads, bos_create / bos_destroy), solver_step.hip (the GN step, its graphs and the step's entry
 // points), solver_shard.hip (the multi-rank phases and exchanges), solver_lm.hip (bos_cost / bos_optimize)
-// and the covariance calls, which share cov_call.hpp: solver_cov.hip (marginals and edge covariances),
+// and the covariance calls, which share cov_call.hpp: solver_cov.hip (marginals, edge covariances and edge consistency),
 // solver_cov_pair.hip (pair covariances, joint compatibility, JCBB) and solver_cov_node.hip (node covariances,
 // bearing association, node matching). The handle owns every device buffer (mem), the static plan
 // (host/plan.hpp), the rocSOLVER refactorization state and the RCCL communicator.
@@ -23,6 +23,7 @@
 #include "../host/plan.hpp"
 #include "associate.hpp"
 #include "device_mem.hpp"
+#include "edge_check.hpp"
 #include "jcbb.hpp"
 #include "joint.hpp"
 #include "kernels.hpp"
@@ -222,6 +223,11 @@ struct bos_solver {
     double jcbb_ms[7] = {};
     std::vector<int64_t> jcbb_nodes;
     int64_t jcbb_batch = 0;
+    // bos_edge_consistency (hip/edge_check.hpp): the feature's arena, built at the first call (with the edge
+    // call's state and the cost pass's fp64 measurements, which it reads); the last call's split (host
+    // preparation, J+H, factorization, selected inverse + emission, projection + scoring, selection, download)
+    bos::dev::EdgeCheck* edge_check = nullptr;
+    double check_ms[7] = {};
     // ---- bos_cost / bos_optimize (hip/lm.hpp). The fp64 originals of what the cost pass reads and the
     // J+H keeps only in T: odometry z / information (upper triangle) and the bearing weights (has_w)
     std::vector<double> h_oz, h_oom, h_bw;
@@ -299,6 +305,8 @@ int launch_rccl_step(bos_solver* s, bool sync);
 int do_step_sharded(bos_solver* s, bos_step_stats* st, bool sync);
 // solver_lm.hip
 int enqueue_lm_iteration(bos_solver* s);
+// the cost pass's buffers (the fp64 measurements among them) at their first use
+int lm_buffers_setup(bos_solver* s);
 
 }  // namespace capi
 }  // namespace bos

@@ -132,6 +132,8 @@ int launch_lm_iteration(bos_solver* s) {
 namespace bos {
 namespace capi {
 
+int lm_buffers_setup(bos_solver* s) { return lm_setup(s); }
+
 // The device work of one LM iteration (multifrontal handles, one GPU): the undamped J+H, lambda from
 // device memory onto its diagonal (the same launch backs the state up), the step's own solve, the
 // model's predicted reduction, the trial box-plus, the fp64 cost of the trial state, the decision (host/lm_rule.hpp) and

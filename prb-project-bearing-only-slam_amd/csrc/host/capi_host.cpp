@@ -16,6 +16,7 @@
 #include "match.hpp"
 #include "jcbb.hpp"
 #include "joint.hpp"
+#include "edge_check.hpp"
 #include "edge_cov.hpp"
 #include "node_cov.hpp"
 #include "pair_cov.hpp"
@@ -505,6 +506,86 @@ int bos_plan_mf_edge_covariances(const bos_problem* pb, const bos_options* optio
     for (int64_t e = 0; e < pi.Mo; ++e) bos::edge_cov_odometry(in, o, e);
     if (pose_cov) std::copy(pc.begin(), pc.end() - 1, pose_cov);
     if (landmark_cov) std::copy(lc.begin(), lc.end() - 1, landmark_cov);
+    return BOS_OK;
+}
+
+namespace {
+// One kind's lists of bos_plan_mf_edge_consistency: the edges whose w2 is finite and >= gate in a stable sort,
+// descending (equal w2 keep the lower index first), the k first listed with their e (D doubles) and T (D x D)
+void edge_check_lists(const std::vector<double>& w2, double gate, size_t k, size_t D, const std::vector<double>& e, const std::vector<double>& T,
+                      int32_t* cand, double* cand_w2, double* cand_e, double* cand_T, int32_t* n_over) {
+    std::vector<int32_t> over;
+    for (size_t i = 0; i < w2.size(); ++i)
+        if (std::isfinite(w2[i]) && w2[i] >= gate) over.push_back((int32_t)i);
+    std::stable_sort(over.begin(), over.end(), [&](int32_t x, int32_t y) { return w2[x] > w2[y]; });
+    for (size_t j = 0; j < k; ++j) {
+        const bool listed = j < over.size();
+        const size_t i = listed ? (size_t)over[j] : 0;
+        if (cand) cand[j] = listed ? over[j] : -1;
+        if (cand_w2) cand_w2[j] = listed ? w2[i] : -HUGE_VAL;
+        for (size_t v = 0; v < D && cand_e; ++v) cand_e[j * D + v] = listed ? e[i * D + v] : 0.0;
+        for (size_t v = 0; v < D * D && cand_T; ++v) cand_T[j * D * D + v] = listed ? T[i * D * D + v] : 0.0;
+    }
+    if (n_over) *n_over = (int32_t)over.size();
+}
+}  // namespace
+
+// Test hook: bos_edge_consistency in its literal host form: bearing_var / odom_cov of
+// bos_plan_mf_edge_covariances, the per-edge evaluation of edge_check.hpp at the problem's state (theta wrapped
+// as bos_create wraps it, Omega by its upper triangle), then a plain stable sort per kind.
+int bos_plan_mf_edge_consistency(const bos_problem* pb, const bos_options* options, const double* vals, double gate_bearing,
+                                 double gate_odom, int32_t k, int32_t* cand_bearing, double* cand_bearing_w2,
+                                 double* cand_bearing_innovation, double* cand_bearing_resvar, int32_t* n_over_bearing,
+                                 int32_t* cand_odom, double* cand_odom_w2, double* cand_odom_innovation, double* cand_odom_rescov,
+                                 int32_t* n_over_odom, double* bearing_w2, double* bearing_chi2, double* bearing_redundancy,
+                                 double* odom_w2, double* odom_chi2, double* odom_redundancy) {
+    if (!pb || !vals || !pb->pose_xyt || (!pb->landmark_xy && pb->num_landmarks > 0)) return hfail(BOS_ERR_INVALID, "null argument");
+    if (const char* bad = bos::edge_check_bad_argument(gate_bearing, gate_odom, k))
+        return hfail(BOS_ERR_INVALID, std::string("bos_edge_consistency: ") + bad);
+    const size_t Mb = (size_t)pb->num_bearings, Mo = (size_t)pb->num_odometry, NP = (size_t)pb->num_poses;
+    // P: zero everywhere when the fixed pose is the only node (there is no system then)
+    std::vector<double> var(Mb + 1, 0.0), cov(9 * Mo + 1, 0.0);
+    if (3 * (NP - 1) + 2 * (size_t)pb->num_landmarks > 0) {
+        const int rc = bos_plan_mf_edge_covariances(pb, options, vals, nullptr, nullptr, var.data(), cov.data(), nullptr, nullptr);
+        if (rc) return rc;
+    }
+    std::vector<double> pose(pb->pose_xyt, pb->pose_xyt + 3 * NP);
+    for (size_t i = 0; i < NP; ++i) pose[3 * i + 2] = bos::normalized_angle<double>(bos::smallest_angle<double>(pose[3 * i + 2]));
+    std::vector<double> bw(Mb), be(Mb), bT(Mb);
+    for (size_t i = 0; i < Mb; ++i) {
+        const size_t p = (size_t)pb->bearing_pose[i], l = (size_t)pb->bearing_landmark[i];
+        const double th = pose[3 * p + 2];
+        double gx, gy;
+        const double e = bos::bearing_error<double>(pose[3 * p], pose[3 * p + 1], std::cos(th), std::sin(th), pb->landmark_xy[2 * l],
+                                                    pb->landmark_xy[2 * l + 1], pb->bearing_z[i], gx, gy);
+        const bos::EdgeCheckBearing r = bos::edge_check_bearing(e, pb->bearing_omega ? pb->bearing_omega[i] : 1.0, var[i]);
+        bw[i] = r.w2; be[i] = r.e; bT[i] = r.T;
+        if (bearing_w2) bearing_w2[i] = r.w2;
+        if (bearing_chi2) bearing_chi2[i] = r.chi2;
+        if (bearing_redundancy) bearing_redundancy[i] = r.redundancy;
+    }
+    std::vector<double> ow(Mo), oe(3 * Mo), oT(9 * Mo);
+    for (size_t j = 0; j < Mo; ++j) {
+        const size_t a = (size_t)pb->odom_src[j], d = (size_t)pb->odom_dst[j];
+        const double* m = pb->odom_omega + 9 * j;
+        const double* z = pb->odom_z + 3 * j;
+        const double u[6] = {m[0], m[1], m[2], m[4], m[5], m[8]};
+        double e[3], J[18], R[6];
+        bos::odometry_error_jacobian<double>(pose[3 * a], pose[3 * a + 1], pose[3 * a + 2], std::cos(pose[3 * a + 2]), std::sin(pose[3 * a + 2]),
+                                             pose[3 * d], pose[3 * d + 1], pose[3 * d + 2], z[0], z[1], z[2], e, J);
+        bos::edge_check_information_inverse(u, R);
+        bos::EdgeCheckOdom r;
+        bos::edge_check_odometry(e, u, R, cov.data() + 9 * j, a == d, r);
+        ow[j] = r.w2;
+        std::copy_n(r.e, 3, oe.begin() + 3 * j);
+        std::copy_n(r.T, 9, oT.begin() + 9 * j);
+        if (odom_w2) odom_w2[j] = r.w2;
+        if (odom_chi2) odom_chi2[j] = r.chi2;
+        if (odom_redundancy) odom_redundancy[j] = r.redundancy;
+    }
+    edge_check_lists(bw, gate_bearing, (size_t)k, 1, be, bT, cand_bearing, cand_bearing_w2, cand_bearing_innovation, cand_bearing_resvar,
+                     n_over_bearing);
+    edge_check_lists(ow, gate_odom, (size_t)k, 3, oe, oT, cand_odom, cand_odom_w2, cand_odom_innovation, cand_odom_rescov, n_over_odom);
     return BOS_OK;
 }
 
