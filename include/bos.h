@@ -752,6 +752,49 @@ int bos_cost(struct bos_solver* s, double* cost, double* chi2, int32_t* n_robust
  * stays usable. */
 int bos_optimize(struct bos_solver* s, const bos_lm_options* options, bos_lm_result* result,
                  bos_lm_iteration* trace, int32_t trace_capacity);
+/*
+ * Unary prior factors: a Gaussian prior (mean, information Omega) on single poses and single landmarks, added to
+ * every H and b the handle builds (DESIGN.md §4 "Priors"). Each call REPLACES the handle's whole prior set;
+ * n_pose == 0 && n_landmark == 0 clears it. The caller's arrays are copied. pose / landmark are node indices
+ * (at most one prior per node and kind), pose_mean [n][3] = (x, y, theta), pose_omega [n][9] and
+ * landmark_omega [n][4] row-major (the upper triangle is what is kept), landmark_mean [n][2].
+ * Every line is one IEEE operation at a time, without FP contraction (csrc/host/prior.hpp, exported as
+ * bos_prior_terms in bos_host.h). Pose prior at pose (x, y, theta), mean m, u = (00, 01, 02, 11, 12, 22) of Omega;
+ * the perturbation is left-multiplicative, so J = [[1, 0, -y], [0, 1, x], [0, 0, 1]]:
+ *   e0 = x - m0, e1 = y - m1, e2 = normalized_angle(theta - m2)
+ *   Oe0 = (u00 e0 + u01 e1) + u02 e2, Oe1 = (u01 e0 + u11 e1) + u12 e2, Oe2 = (u02 e0 + u12 e1) + u22 e2
+ *   rho = (e0 Oe0 + e1 Oe1) + e2 Oe2
+ *   g = J^T Omega e:  g0 = Oe0, g1 = Oe1, g2 = ((-y) Oe0 + x Oe1) + Oe2
+ *   q = Omega (-y, x, 1)^T:  q0 = ((-y) u00 + x u01) + u02, q1 = ((-y) u01 + x u11) + u12, q2 = ((-y) u02 + x u12) + u22
+ *   A = J^T Omega J, lower triangle (00, 10, 11, 20, 21, 22) = (u00, u01, u11, q0, q1, ((-y) q0 + x q1) + q2)
+ * Landmark prior at l, mean m, u = (00, 01, 11), J = I:
+ *   e = l - m,  g0 = u00 e0 + u01 e1, g1 = u01 e0 + u11 e1,  rho = e0 g0 + e1 g1,  A = (u00, u01, u11)
+ * Priors are not robustified (h(rho) = rho) and b accumulates J^T Omega e like every edge (H x_s = b, dx = -x_s).
+ * The J+H build is followed by one kernel, a thread per prior, that forms A and g in the handle's precision
+ * from the state caches the build reads and adds them to the node's diagonal block and b segment; a handle
+ * without priors launches exactly what it launched before. Addition order: bos_step, bos_linearize and the
+ * covariance calls build H = (sum over edges + damping) + A; bos_optimize builds (sum over edges + A) + lambda,
+ * its lambda being added after the prior kernel. So on a handle with priors "an LM iteration with lambda = d is
+ * the linear system of a bos_step with damping factor d" holds to rounding, not in its bits.
+ * bos_step_stats.chi2, bos_cost's cost and chi2 and bos_optimize's F include the sum of rho over the priors (the
+ * step's in the handle's precision, reduced in a fixed order; bos_cost's in fp64 from the master state);
+ * n_robust does not count priors. Every covariance and gate call (bos_marginals, bos_edge_covariances,
+ * bos_pair_covariances, bos_node_covariances, bos_associate_bearings, bos_match_*, bos_joint_compatibility,
+ * bos_jcbb, bos_edge_consistency) sees H with the priors; nothing else about those calls changes. Priors are not
+ * rows of bos_edge_consistency, and on a handle with priors the trace identity of its comment reads
+ *   sum over edges tr(Omega P) + sum over priors tr(Omega_k J_k Sigma_kk J_k^T) = n - lambda tr(Sigma).
+ * Priors survive bos_set_state, bos_triangulate and bos_optimize. The call drops the captured step graphs and
+ * the captured LM iteration; the next step captures them again with the new set.
+ * BOS_ERR_INVALID, with nothing touched, for: an index outside [0, num_poses) / [0, num_landmarks); a node
+ * listed twice within its kind; the fixed pose; a mean that is not finite; an Omega that is not finite, not
+ * bit-symmetric or has a negative diagonal entry. A semidefinite Omega (heading only, position only) is
+ * allowed; an indefinite one is the caller's risk and shows in solver_info. Every one-GPU handle (all four
+ * solvers, both precisions); BOS_ERR_UNSUPPORTED on sharded handles. BOS_ERR_DEVICE (bos_last_error names the
+ * byte count) when the buffers cannot be allocated: the handle stays usable and keeps its previous set.
+ */
+int bos_set_priors(struct bos_solver* s, int32_t n_pose, const int32_t* pose, const double* pose_mean,
+                   const double* pose_omega, int32_t n_landmark, const int32_t* landmark, const double* landmark_mean,
+                   const double* landmark_omega);
 
 /* Diagnostics: the phase boundaries of the last completed step, realtime clock (100 MHz ticks),
  * as the step's own kernels stamped them: [0] J+H start, [1] J+H end / solve start, [2] solve end,

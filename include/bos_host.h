@@ -255,6 +255,19 @@ int bos_cpu_gn_set_kernel_threshold(bos_cpu_gn* c, double kt);
 int bos_cpu_gn_cost(bos_cpu_gn* c, double* cost, double* chi2, int32_t* n_robust);
 int bos_cpu_gn_optimize(bos_cpu_gn* c, const bos_lm_options* options, bos_lm_result* result, bos_lm_iteration* trace,
                         int32_t trace_capacity);
+/* The CPU twin of bos_set_priors (include/bos.h): the same arguments, checks and "replace" semantics; the
+ * object's step, cost and optimize then include the priors in fp64 through the same functions
+ * (csrc/host/prior.hpp), added in the device's order (after the J+H build, before an LM iteration's lambda). */
+int bos_cpu_gn_set_priors(bos_cpu_gn* c, int32_t n_pose, const int32_t* pose, const double* pose_mean, const double* pose_omega,
+                          int32_t n_landmark, const int32_t* landmark, const double* landmark_mean,
+                          const double* landmark_omega);
+/* Test hook: the terms of one prior in fp64 by the functions the prior kernel, the cost pass and the CPU twin
+ * call (csrc/host/prior.hpp; the formulas are written out at bos_set_priors). kind 0: a pose prior,
+ * node_state = (x, y, theta), mean[3], omega[9] row-major, A[6] = (00, 10, 11, 20, 21, 22), g[3]. kind 1: a
+ * landmark prior, node_state = (x, y), mean[2], omega[4], A[3] = (00, 10, 11), g[2]. Only the upper triangle
+ * of omega is read. *rho = e^T Omega e. */
+int bos_prior_terms(int32_t kind, const double* node_state, const double* mean, const double* omega, double* A, double* g,
+                    double* rho);
 
 /* The LM step control's state between two iterations (the device keeps one per handle). */
 typedef struct bos_lm_state { double lambda, nu, cost; int32_t iteration, accepted, rejected, done, reason; } bos_lm_state;

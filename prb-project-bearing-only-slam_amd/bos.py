@@ -70,6 +70,7 @@ EXPORTED_SYMBOLS = [
     "bos_joint_compatibility", "bos_plan_mf_joint_compatibility", "bos_joint_compatibility_timing",
     "bos_debug_set_joint_batch",
     "bos_jcbb", "bos_jcbb_search_host", "bos_plan_mf_jcbb", "bos_jcbb_timing", "bos_debug_set_jcbb_batch",
+    "bos_set_priors", "bos_cpu_gn_set_priors", "bos_prior_terms",
 ]
 
 # bos_lm_result.reason
@@ -280,6 +281,9 @@ def lib():
         "bos_optimize": (ctypes.c_int, [vp, ctypes.POINTER(bos_lm_options), ctypes.POINTER(bos_lm_result),
                                         ctypes.POINTER(bos_lm_iteration), ctypes.c_int32]),
         "bos_time_cost": (ctypes.c_int, [vp, ctypes.c_int32, _dp]),
+        "bos_set_priors": (ctypes.c_int, [vp, ctypes.c_int32, _ip, _dp, _dp, ctypes.c_int32, _ip, _dp, _dp]),
+        "bos_cpu_gn_set_priors": (ctypes.c_int, [vp, ctypes.c_int32, _ip, _dp, _dp, ctypes.c_int32, _ip, _dp, _dp]),
+        "bos_prior_terms": (ctypes.c_int, [ctypes.c_int32, _dp, _dp, _dp, _dp, _dp, _dp]),
         "bos_cpu_gn_set_kernel_threshold": (ctypes.c_int, [vp, ctypes.c_double]),
         "bos_cpu_gn_cost": (ctypes.c_int, [vp, _dp, _dp, _ip]),
         "bos_cpu_gn_optimize": (ctypes.c_int, [vp, ctypes.POINTER(bos_lm_options), ctypes.POINTER(bos_lm_result),
@@ -1139,6 +1143,44 @@ def _run_cost(fn, h, what) -> dict:
     return {"cost": F.value, "chi2": chi.value, "n_robust": nrob.value}
 
 
+def _prior_arrays(prior, dim: int):
+    """(index, mean, omega) -> contiguous (n, int32 [n], float64 [n, dim], float64 [n, dim, dim]); None: no priors."""
+    if prior is None:
+        return 0, None, None, None
+    index, mean, omega = prior
+    idx = np.ascontiguousarray(np.asarray(index, dtype=np.int32).reshape(-1))
+    n = idx.size
+    if n == 0:
+        return 0, None, None, None
+    m = np.ascontiguousarray(np.asarray(mean, dtype=np.float64).reshape(n, dim))
+    om = np.ascontiguousarray(np.asarray(omega, dtype=np.float64).reshape(n, dim, dim))
+    return n, idx, m, om
+
+
+def _set_priors(fn, h, what, pose, landmark):
+    npp, pi, pm, po = _prior_arrays(pose, 3)
+    nl, li, lmn, lo = _prior_arrays(landmark, 2)
+    _check(fn(h, npp, _ptr(pi, ctypes.c_int32), _ptr(pm, ctypes.c_double), _ptr(po, ctypes.c_double),
+              nl, _ptr(li, ctypes.c_int32), _ptr(lmn, ctypes.c_double), _ptr(lo, ctypes.c_double)), what)
+
+
+def prior_terms(kind: str, node_state, mean, omega):
+    """The terms of one prior in fp64 (bos_prior_terms): kind "pose" (state and mean of 3, omega 3 x 3) or
+    "landmark" (2, 2 x 2). Returns (A, g, rho): A the lower triangle (00, 10, 11[, 20, 21, 22]) of J^T Omega J,
+    g = J^T Omega e, rho = e^T Omega e."""
+    dim = {"pose": 3, "landmark": 2}[kind]
+    x = np.ascontiguousarray(np.asarray(node_state, dtype=np.float64).reshape(dim))
+    m = np.ascontiguousarray(np.asarray(mean, dtype=np.float64).reshape(dim))
+    om = np.ascontiguousarray(np.asarray(omega, dtype=np.float64).reshape(dim, dim))
+    A = np.zeros(dim * (dim + 1) // 2)
+    g = np.zeros(dim)
+    rho = ctypes.c_double(0)
+    _check(lib().bos_prior_terms(0 if kind == "pose" else 1, _ptr(x, ctypes.c_double), _ptr(m, ctypes.c_double),
+                                 _ptr(om, ctypes.c_double), _ptr(A, ctypes.c_double), _ptr(g, ctypes.c_double),
+                                 ctypes.byref(rho)), "bos_prior_terms")
+    return A, g, rho.value
+
+
 class CpuGN:
     """The CPU baseline of bench.py (include/bos_host.h bos_cpu_gn_*): the same GN iteration on the
     host's cores with the build's own host multifrontal Cholesky. Not a fallback of Solver."""
@@ -1156,6 +1198,10 @@ class CpuGN:
 
     def set_kernel_threshold(self, kt: float):
         _check(lib().bos_cpu_gn_set_kernel_threshold(self._h, kt), "bos_cpu_gn_set_kernel_threshold")
+
+    def set_priors(self, pose=None, landmark=None):
+        """The CPU twin of Solver.set_priors (bos_cpu_gn_set_priors): same arguments, replaces the set."""
+        _set_priors(lib().bos_cpu_gn_set_priors, self._h, "bos_cpu_gn_set_priors", pose, landmark)
 
     def cost(self) -> dict:
         """The objective at the current state (bos_cpu_gn_cost): cost, chi2, n_robust."""
@@ -1237,6 +1283,16 @@ class Solver:
 
     def set_damping_factor(self, df: float):
         _check(lib().bos_set_damping_factor(self._h, df), "set_damping_factor")
+
+    def set_priors(self, pose=None, landmark=None):
+        """Unary prior factors (bos_set_priors): pose = (index [n], mean [n, 3], omega [n, 3, 3]), landmark =
+        (index [n], mean [n, 2], omega [n, 2, 2]), either may be None. Replaces the handle's whole prior set;
+        every H, b, chi2 and cost the handle computes afterwards includes the priors."""
+        _set_priors(lib().bos_set_priors, self._h, "bos_set_priors", pose, landmark)
+
+    def clear_priors(self):
+        """Removes every prior (bos_set_priors with two empty sets)."""
+        self.set_priors(None, None)
 
     def step(self) -> dict:
         st = bos_step_stats()

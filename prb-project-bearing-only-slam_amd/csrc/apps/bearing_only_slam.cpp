@@ -1,6 +1,9 @@
 // Headless drop-in for executables/bearing_only_slam.cpp (reference :40-116).
 // Usage: bearing_only_slam <dataset_fname> [--iters N] [--lm] [--fp32] [--dense|--schur] [--dump out.g2o]
-//                          [--ppm out.ppm] [--check-edges K] [--quiet]
+//                          [--ppm out.ppm] [--check-edges K] [--anchor map.g2o --anchor-sigma S] [--quiet]
+// --anchor FILE.g2o: the known-map run. Every landmark whose id also occurs in FILE gets a prior
+// (bos_set_priors) at FILE's position with information I / S^2 (--anchor-sigma S, default 0.1); the count and,
+// after the run, the priors' sum of rho are printed.
 // --lm: Levenberg-Marquardt (bos_optimize, at most --iters iterations, it stops by itself) instead of
 // the fixed count of Gauss-Newton steps; one line per iteration.
 // --check-edges K: after the run, the K (1 .. 8) bearings and odometry edges with the largest normalised residual
@@ -19,6 +22,7 @@
 
 #include "../host/draw_ppm.hpp"
 #include "../host/g2o_utils.hpp"
+#include "../host/prior.hpp"
 #include "../host/solver.hpp"
 #include "../host/triangulation.hpp"
 
@@ -27,13 +31,14 @@ using namespace proj02;
 int main(int argc, char** argv) {
     if (argc < 2) {
         std::cout << "usage: bearing_only_slam <dataset_fname> [--iters N] [--lm] [--fp32] [--dense|--schur] [--dump out.g2o] "
-                     "[--ppm out.ppm] [--check-edges K] [--quiet]"
+                     "[--ppm out.ppm] [--check-edges K] [--anchor map.g2o --anchor-sigma S] [--quiet]"
                   << std::endl;
         return 1;
     }
     int iters = 50, check_edges = 0;
     bool quiet = false, lm = false;
-    std::string dump, ppm;
+    std::string dump, ppm, anchor;
+    double anchor_sigma = 0.1;
     bos_options opt;
     bos_default_options(&opt);
     for (int i = 2; i < argc; ++i) {
@@ -45,6 +50,8 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--dump") && i + 1 < argc) dump = argv[++i];
         else if (!std::strcmp(argv[i], "--ppm") && i + 1 < argc) ppm = argv[++i];
         else if (!std::strcmp(argv[i], "--check-edges") && i + 1 < argc) check_edges = std::atoi(argv[++i]);
+        else if (!std::strcmp(argv[i], "--anchor") && i + 1 < argc) anchor = argv[++i];
+        else if (!std::strcmp(argv[i], "--anchor-sigma") && i + 1 < argc) anchor_sigma = std::atof(argv[++i]);
         else if (!std::strcmp(argv[i], "--quiet")) quiet = true;
         else { std::cerr << "unknown argument " << argv[i] << std::endl; return 1; }
     }
@@ -67,6 +74,36 @@ int main(int argc, char** argv) {
     if (!ppm.empty()) render(state, ppm.substr(0, ppm.rfind('.')) + "_initial.ppm");
     try {
         Solver solver(state, bearings, odometries, fixed_pose_id, &opt);
+        // the anchored landmarks (stix), their means and the information, as bos_set_priors takes them
+        std::vector<int32_t> anchored;
+        std::vector<double> anchor_mean, anchor_omega;
+        if (!anchor.empty()) {
+            if (!(anchor_sigma > 0.0)) throw std::runtime_error("--anchor-sigma must be positive");
+            State map(300, 200);
+            BearingObservationVector mb;
+            OdometryObservationVector mo;
+            int mfixed = -1;
+            float mbound = 0;
+            if (parse_g2o(anchor, map, mb, mo, mfixed, mbound)) throw std::runtime_error("cannot read " + anchor);
+            const double w = 1.0 / (anchor_sigma * anchor_sigma);
+            const AssociationVec& ids = state.landmark_ids();
+            for (int l = 0; l < (int)ids.size(); ++l) {
+                LMPos m;
+                try {
+                    m = map.get_landmark_by_id(ids[l]);
+                } catch (const std::out_of_range&) {
+                    continue;
+                }
+                anchored.push_back(l);
+                anchor_mean.insert(anchor_mean.end(), {m.x, m.y});
+                anchor_omega.insert(anchor_omega.end(), {w, 0.0, 0.0, w});
+            }
+            if (bos_set_priors(solver.handle(), 0, nullptr, nullptr, nullptr, (int32_t)anchored.size(), anchored.data(),
+                               anchor_mean.data(), anchor_omega.data()) != BOS_OK)
+                throw std::runtime_error(bos_last_error());
+            std::printf("anchored %d of %d landmarks to %s (sigma %g)\n", (int)anchored.size(), (int)ids.size(), anchor.c_str(),
+                        anchor_sigma);
+        }
         if (lm) {
             bos_lm_options lo;
             bos_lm_default_options(&lo);
@@ -91,6 +128,17 @@ int main(int argc, char** argv) {
             if (!quiet)
                 std::printf("iter %3d  chi2 %.9g  robust %d  max|dx| %.3g  J+H %.3f ms  solve %.3f ms\n", it, s.chi2,
                             s.n_robust, s.max_abs_dx, s.t_linearize_ms, s.t_solve_ms);
+        }
+        if (!anchor.empty()) {   // sum of rho = e^T Omega e over the priors at the final state
+            const State& final_state = solver.state;   // the reading overload: a write would re-upload the state
+            const LMPosVector& lms = final_state.landmarks_vec();
+            const double w = 1.0 / (anchor_sigma * anchor_sigma);
+            double rho = 0.0;
+            for (size_t i = 0; i < anchored.size(); ++i) {
+                const double u[3] = {w, 0.0, w};
+                rho += bos::prior_landmark_rho<double>(lms[anchored[i]].x, lms[anchored[i]].y, &anchor_mean[2 * i], u);
+            }
+            std::printf("anchors: sum of rho %.9g over %d priors\n", rho, (int)anchored.size());
         }
         if (check_edges != 0) {
             const int k = check_edges;

@@ -640,7 +640,7 @@ __device__ __forceinline__ void sum_partials(const double* chi_part, const int32
 
 __global__ void reduce_stats_kernel(const double* chi_part, const int32_t* nrob_part, int n, double chi_const,
                                     int32_t nrob_const, const double* max_part, int n_max, int32_t* info,
-                                    StepStatus* out, StepStatus* mirror) {
+                                    StepStatus* out, StepStatus* mirror, const double* prior_part, int n_prior) {
     __shared__ double sc[256];
     __shared__ double sm[256];
     __shared__ long long sr[256];
@@ -653,6 +653,8 @@ __global__ void reduce_stats_kernel(const double* chi_part, const int32_t* nrob_
         c = chi_part[0];
         r = (long long)chi_part[1];
     }
+    // the prior kernel's sums of rho (hip/prior.hpp), dealt to the threads in a fixed stride
+    for (int i = threadIdx.x; i < n_prior; i += blockDim.x) c += prior_part[i];
     if (max_part)
         for (int i = threadIdx.x; i < n_max; i += blockDim.x) m = nan_max(m, max_part[i]);
     sc[threadIdx.x] = c;
@@ -1192,9 +1194,9 @@ template <typename T> hipError_t launch_triangulate(const TriParams<T>& p, hipSt
 
 hipError_t launch_reduce_stats(const double* chi_part, const int32_t* nrob_part, int n, double chi_const,
                                int32_t nrob_const, const double* max_part, int n_max, int32_t* info,
-                               StepStatus* out, StepStatus* mirror, hipStream_t s) {
+                               StepStatus* out, StepStatus* mirror, hipStream_t s, const double* prior_part, int n_prior) {
     hipLaunchKernelGGL(reduce_stats_kernel, dim3(1), dim3(256), 0, s, chi_part, nrob_part, n, chi_const, nrob_const,
-                       max_part, n_max, info, out, mirror);
+                       max_part, n_max, info, out, mirror, prior_part, prior_part ? n_prior : 0);
     return hipGetLastError();
 }
 

@@ -262,10 +262,12 @@ hipError_t launch_p2p_push_gather(const P2PPush& p, hipStream_t s);
 // propagates) into *out, moves *info into out->info and zeroes *info for the next iteration: one
 // launch replaces the per-step memsets and read-backs. out->aborted is sticky; out->stamp[3] gets the
 // realtime clock at the end. The finished summary is also copied to *mirror (host-mapped memory the
-// host reads after synchronising: no copy launch per step), if set.
+// host reads after synchronising: no copy launch per step), if set. prior_part: the prior kernel's
+// n_prior partial sums of rho (hip/prior.hpp), added to chi^2 in a fixed order; null on a handle without priors.
 hipError_t launch_reduce_stats(const double* chi_part, const int32_t* nrob_part, int n, double chi_const,
                                int32_t nrob_const, const double* max_part, int n_max, int32_t* info,
-                               StepStatus* out, StepStatus* mirror, hipStream_t s);
+                               StepStatus* out, StepStatus* mirror, hipStream_t s, const double* prior_part = nullptr,
+                               int n_prior = 0);
 // Reads n doubles (all of them: the sum is compared with an impossible value), so L2 and the
 // Infinity Cache hold clean lines of this buffer afterwards (cold-cache timing, bos_time_linearize).
 hipError_t launch_cache_scrub(const double* buf, int64_t n, double* sink, hipStream_t s);

@@ -5,6 +5,7 @@
 #include <algorithm>
 
 #include "../host/bos_math.hpp"
+#include "../host/prior.hpp"
 #include "kernels.hpp"
 
 namespace bos {
@@ -80,12 +81,36 @@ __device__ __forceinline__ bool edge_rho(const CostParams& P, int64_t i, double&
     return true;
 }
 
+// rho of prior k (pose priors, then landmark priors) at the master state; false for a node outside the state
+__device__ __forceinline__ bool prior_rho(const CostParams& P, int64_t k, double& rho) {
+    const int node = P.pr_idx[k];
+    if (k < P.n_pose_priors) {
+        if (node < 0 || node >= P.NP) return false;
+        const double* x = P.pose + 3 * (int64_t)node;
+        const double* r = P.pr_pose + 9 * k;
+        rho = bos::prior_pose_rho<double>(x[0], x[1], x[2], r, r + 3);
+        return true;
+    }
+    if (node < 0 || node >= P.NL) return false;
+    const double* l = P.lm + 2 * (int64_t)node;
+    const double* r = P.pr_lm + 5 * (k - P.n_pose_priors);
+    rho = bos::prior_landmark_rho<double>(l[0], l[1], r, r + 2);
+    return true;
+}
+
 __global__ __launch_bounds__(kLmBlock) void lm_cost_kernel(const CostParams P) {
     __shared__ double sh[kLmBlock / 64];
-    const int64_t total = (int64_t)P.Mb + P.Mo, stride = (int64_t)gridDim.x * kLmBlock;
+    const int64_t edges = (int64_t)P.Mb + P.Mo, total = edges + P.n_pose_priors + P.n_lm_priors;
+    const int64_t stride = (int64_t)gridDim.x * kLmBlock;
     double f = 0.0, chi = 0.0, nr = 0.0;
     for (int64_t i = (int64_t)blockIdx.x * kLmBlock + threadIdx.x; i < total; i += stride) {
         double rho;
+        if (i >= edges) {   // a prior: h(rho) = rho
+            if (!prior_rho(P, i - edges, rho)) continue;
+            f += rho;
+            chi += rho;
+            continue;
+        }
         if (!edge_rho(P, i, rho)) continue;
         const bool rob = rho > P.kt;
         f += bos::lm_huber(rho, P.kt, rob ? sqrt(P.kt * rho) : 0.0);

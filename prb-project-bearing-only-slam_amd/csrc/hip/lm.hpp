@@ -35,7 +35,8 @@ struct LmControl {
 
 // F, chi^2 and the robust count at the master state: the edges dealt to the threads in a fixed
 // stride, bearings [0, Mb) in measurement order then odometry edges [Mb, Mb + Mo) (self-loops
-// contribute nothing here: they are constants the caller adds), one partial of each per workgroup.
+// contribute nothing here: they are constants the caller adds), then the pose priors and the landmark
+// priors (bos_set_priors; not robustified: F and chi^2 both gain rho), one partial of each per workgroup.
 struct CostParams {
     int NP, NL, Mb, Mo;
     const double* pose;       // [NP][3]
@@ -48,17 +49,23 @@ struct CostParams {
     const int32_t* o_dst;     // [Mo]
     const double* o_z;        // [Mo][3]
     const double* o_om;       // [Mo][6] upper triangle (00, 01, 02, 11, 12, 22)
+    // priors (host/prior.hpp), fp64: node of each (pose priors, then landmark priors), mean[3] + upper
+    // triangle[6] per pose prior, mean[2] + upper triangle[3] per landmark prior
+    int n_pose_priors = 0, n_lm_priors = 0;
+    const int32_t* pr_idx = nullptr;
+    const double* pr_pose = nullptr;
+    const double* pr_lm = nullptr;
     double kt;
     double* part_F;           // [n_parts]
     double* part_chi;         // [n_parts]
     int32_t* part_nrob;       // [n_parts]
-    int n_parts;              // workgroups: lm_cost_parts(Mb, Mo)
+    int n_parts;              // workgroups: lm_cost_parts(Mb, Mo, priors)
 };
 inline int lm_parts(int64_t items) {
     const int64_t b = (items + kLmBlock - 1) / kLmBlock;
     return (int)(b < kLmMaxParts ? b : kLmMaxParts);
 }
-inline int lm_cost_parts(int64_t Mb, int64_t Mo) { return lm_parts(Mb + Mo); }
+inline int lm_cost_parts(int64_t Mb, int64_t Mo, int64_t priors = 0) { return lm_parts(Mb + Mo + priors); }
 hipError_t launch_lm_cost(const CostParams& p, hipStream_t s);
 
 // Word copies of up to five arrays in one launch (the state and its T caches).

@@ -1,6 +1,6 @@
 // The C ABI handle (include/bos.h) and what its implementation files share: solver_create.hip (plan,
 // uploads, bos_create / bos_destroy), solver_step.hip (the GN step, its graphs and the step's entry
-// points), solver_shard.hip (the multi-rank phases and exchanges), solver_lm.hip (bos_cost / bos_optimize)
+// points), solver_prior.hip (bos_set_priors), solver_shard.hip (the multi-rank phases and exchanges), solver_lm.hip (bos_cost / bos_optimize)
 // and the covariance calls, which share cov_call.hpp: solver_cov.hip (marginals, edge covariances and edge consistency),
 // solver_cov_pair.hip (pair covariances, joint compatibility, JCBB) and solver_cov_node.hip (node covariances,
 // bearing association, node matching). The handle owns every device buffer (mem), the static plan
@@ -32,6 +32,7 @@
 #include "multifrontal.hpp"
 #include "node_cov.hpp"
 #include "pair_cov.hpp"
+#include "prior.hpp"
 #include "selinv.hpp"
 
 #define HIP_TRY(expr)                                                                                  \
@@ -228,6 +229,15 @@ struct bos_solver {
     // preparation, J+H, factorization, selected inverse + emission, projection + scoring, selection, download)
     bos::dev::EdgeCheck* edge_check = nullptr;
     double check_ms[7] = {};
+    // bos_set_priors (hip/prior.hpp, solver_prior.hip): the current set in one allocation of mem (null:
+    // no priors). Nodes (pose priors, then landmark priors), the records in T the prior kernel reads, their
+    // fp64 originals (mean[3] + upper triangle[6] per pose prior, mean[2] + [3] per landmark prior) for the
+    // cost pass, and the kernel's chi^2 partials
+    int n_pose_priors = 0, n_lm_priors = 0;
+    char* prior_arena = nullptr;
+    int32_t* pr_idx = nullptr;
+    void *pr_pose = nullptr, *pr_lm = nullptr;
+    double *pr_pose64 = nullptr, *pr_lm64 = nullptr, *pr_part = nullptr;
     // ---- bos_cost / bos_optimize (hip/lm.hpp). The fp64 originals of what the cost pass reads and the
     // J+H keeps only in T: odometry z / information (upper triangle) and the bearing weights (has_w)
     std::vector<double> h_oz, h_oom, h_bw;
@@ -261,6 +271,7 @@ inline int fail(int code, const std::string& msg) { return bos::set_error(code, 
 inline bool uses_mf(const bos_solver* s) {
     return s->solver_kind == BOS_SOLVER_SUPERNODAL || s->solver_kind == BOS_SOLVER_SCHUR;
 }
+inline int n_priors(const bos_solver* s) { return s->n_pose_priors + s->n_lm_priors; }
 // the block array as the multifrontal solver reads it (fp64)
 inline const double* mf_matrix(const bos_solver* s) {
     return s->precision == BOS_FP32 ? s->d_val64 : (const double*)s->sys_val;

@@ -28,7 +28,8 @@ int lm_setup(bos_solver* s) {
     const bos::Plan& P = s->plan;
     int64_t w[5];
     lm_state_words(s, w);
-    const size_t nc = (size_t)std::max(1, bos::dev::lm_cost_parts(s->Mb, s->Mo));
+    // the partials' room covers any later prior set (at most one prior per node)
+    const size_t nc = (size_t)std::max(1, bos::dev::lm_cost_parts(s->Mb, s->Mo, (int64_t)s->NP + s->NL));
     const size_t nm = (size_t)std::max(1, bos::dev::lm_model_parts(P.n));
     bos::dev::Arena ar;
     ar.add(&s->lm_blm, s->bearing_lm);
@@ -81,9 +82,11 @@ int enqueue_lm_cost(bos_solver* s) {
     c.pose = s->d_pose; c.lm = s->d_lm;
     c.b_pose = s->tri_pose; c.b_lm = s->lm_blm; c.b_z = s->tri_z; c.b_w = s->lm_bw;
     c.o_src = s->o_src; c.o_dst = s->o_dst; c.o_z = s->lm_oz; c.o_om = s->lm_oom;
+    c.n_pose_priors = s->n_pose_priors; c.n_lm_priors = s->n_lm_priors;
+    c.pr_idx = s->pr_idx; c.pr_pose = s->pr_pose64; c.pr_lm = s->pr_lm64;
     c.kt = s->kt;
     c.part_F = s->lm_pF; c.part_chi = s->lm_pchi; c.part_nrob = s->lm_pnrob;
-    c.n_parts = bos::dev::lm_cost_parts(s->Mb, s->Mo);
+    c.n_parts = bos::dev::lm_cost_parts(s->Mb, s->Mo, n_priors(s));
     HIP_TRY(bos::dev::launch_lm_cost(c, s->stream));
     return BOS_OK;
 }
@@ -91,7 +94,7 @@ int enqueue_lm_cost(bos_solver* s) {
 int enqueue_lm_decide(bos_solver* s, int mode) {
     bos::dev::DecideParams d;
     d.part_F = s->lm_pF; d.part_chi = s->lm_pchi; d.part_nrob = s->lm_pnrob;
-    d.n_cost = bos::dev::lm_cost_parts(s->Mb, s->Mo);
+    d.n_cost = bos::dev::lm_cost_parts(s->Mb, s->Mo, n_priors(s));
     lm_loop_terms(s, d.F_const, d.chi_const, d.nrob_const);
     d.part_xx = s->lm_pxx; d.part_xb = s->lm_pxb;
     d.n_model = bos::dev::lm_model_parts(s->plan.n);

@@ -71,6 +71,18 @@ hipError_t launch_jh(bos_solver* s, unsigned long long* t_start, bool undamped, 
     return bos::dev::launch_linearize<double>(p, lpp, s->has_w, s->has_dups, s->stream);
 }
 
+template <typename T> bos::dev::PriorParams<T> prior_params(const bos_solver* s) {
+    bos::dev::PriorParams<T> p;
+    p.n_pose = s->n_pose_priors; p.n_lm = s->n_lm_priors;
+    p.idx = s->pr_idx; p.pose_rec = (const T*)s->pr_pose; p.lm_rec = (const T*)s->pr_lm;
+    p.pc = (const T*)s->d_pc; p.pth = (const T*)s->d_pth; p.lc = (const T*)s->d_lc;
+    p.NP = s->NP; p.NL = s->NL;
+    p.hval = (T*)s->d_val; p.b = (T*)s->d_b;
+    p.off_ldiag = s->plan.blk.off_ldiag; p.nval = s->plan.blk.size;
+    p.part = s->pr_part;
+    return p;
+}
+
 template <typename T> bos::dev::UpdateParams<T> upd_params(const bos_solver* s) {
     bos::dev::UpdateParams<T> u;
     u.NP = s->NP; u.NL = s->NL; u.fixed = s->plan.fixed;
@@ -122,7 +134,8 @@ int enqueue_stats(bos_solver* s, bool with_update) {
     // observations partition: the all-reduced header [chi^2, robust count] instead of the partials
     HIP_TRY(bos::dev::launch_reduce_stats(s->obs ? s->ex1_recv : s->d_chi_part, s->obs ? nullptr : s->d_nrob_part,
                                           s->chi_parts, chi_c, nrob_c, with_update ? s->d_maxpart : nullptr, nupd, info,
-                                          s->d_status, s->m_status, s->stream));
+                                          s->d_status, s->m_status, s->stream, n_priors(s) ? s->pr_part : nullptr,
+                                          bos::dev::prior_parts(n_priors(s))));
     return BOS_OK;
 }
 
@@ -270,6 +283,13 @@ int require_one_gpu(const bos_solver* s, const char* name, bool need_mf, const c
 int enqueue_linearize(bos_solver* s, unsigned long long* t_start, bool undamped) {
     const hipError_t e = launch_jh(s, t_start, undamped, nullptr);
     if (e != hipSuccess) return fail(BOS_ERR_DEVICE, std::string("linearize launch: ") + hipGetErrorString(e));
+    // the priors (bos_set_priors) onto the diagonal blocks and b the build has just written: every
+    // consumer of H comes through here. A handle without priors launches nothing more.
+    if (n_priors(s)) {
+        const hipError_t ep = s->precision == BOS_FP32 ? bos::dev::launch_priors<float>(prior_params<float>(s), s->stream)
+                                                       : bos::dev::launch_priors<double>(prior_params<double>(s), s->stream);
+        if (ep != hipSuccess) return fail(BOS_ERR_DEVICE, std::string("prior launch: ") + hipGetErrorString(ep));
+    }
     return BOS_OK;
 }
 

@@ -23,6 +23,7 @@
 #include "g2o_utils.hpp"
 #include "host_mf.hpp"
 #include "plan.hpp"
+#include "prior.hpp"
 #include "synthetic.hpp"
 #include "triangulation.hpp"
 
@@ -143,6 +144,21 @@ int bos_dataset_load_g2o(const char* path, int triangulate, int verbose, bos_dat
 
 double bos_normalized_angle_f64(double a) { return bos::normalized_angle<double>(a); }
 float bos_normalized_angle_f32(float a) { return bos::normalized_angle<float>(a); }
+
+int bos_prior_terms(int32_t kind, const double* node_state, const double* mean, const double* omega, double* A, double* g,
+                    double* rho) {
+    if (!node_state || !mean || !omega || !A || !g || !rho) return hfail(BOS_ERR_INVALID, "null argument");
+    if (kind == 0) {
+        const double u[6] = {omega[0], omega[1], omega[2], omega[4], omega[5], omega[8]};
+        *rho = bos::prior_pose_terms<double>(node_state[0], node_state[1], node_state[2], mean, u, A, g);
+    } else if (kind == 1) {
+        const double u[3] = {omega[0], omega[1], omega[3]};
+        *rho = bos::prior_landmark_terms<double>(node_state[0], node_state[1], mean, u, A, g);
+    } else {
+        return hfail(BOS_ERR_INVALID, "bos_prior_terms: kind must be 0 (pose) or 1 (landmark)");
+    }
+    return BOS_OK;
+}
 
 int bos_dataset_synthetic(int32_t num_poses, int32_t num_landmarks, int32_t bearings_per_pose, uint64_t seed,
                           bos_dataset** out) {

@@ -18,6 +18,8 @@
 #include "host_mf.hpp"
 #include "lm_rule.hpp"
 #include "plan.hpp"
+#include "prior.hpp"
+#include "prior_set.hpp"
 
 struct bos_cpu_gn {
     bos::Plan plan;
@@ -28,6 +30,7 @@ struct bos_cpu_gn {
     std::vector<int32_t> b_pose, b_lm, o_src, o_dst;
     std::vector<double> b_z, b_w, o_z, o_om;   // o_om: upper triangle (00, 01, 02, 11, 12, 22)
     double kt = 1.0, damping = 0.01;
+    bos::PriorSet priors;   // bos_cpu_gn_set_priors
     // bos_cpu_gn_optimize: the last call's final lambda / nu (lambda0 = 0 continues from them)
     bool lm_started = false;
     double lm_lambda = 0.0, lm_nu = 2.0;
@@ -210,6 +213,25 @@ double cpu_build(bos_cpu_gn* c) {
     pool.parallel_for(NLL, [&](int64_t i) { jh_landmark(c, (int)i); });
     double chi = 0.0;
     for (double v : chi_part) chi += v;
+    // the priors onto the diagonal blocks and b just written (host/prior.hpp), as the device's prior kernel
+    double* hv = c->mf->hval.data();
+    const bos::PriorSet& R = c->priors;
+    for (size_t i = 0; i < R.pose.size(); ++i) {
+        const int p = R.pose[i];
+        const double* r = &R.pose_rec[9 * i];
+        double A[6], g[3];
+        chi += bos::prior_pose_terms<double>(c->pose[3 * (size_t)p], c->pose[3 * (size_t)p + 1], c->pose[3 * (size_t)p + 2], r, r + 3, A, g);
+        for (int q = 0; q < 6; ++q) hv[6 * (int64_t)p + q] += A[q];
+        for (int q = 0; q < 3; ++q) c->b[3 * (size_t)p + q] += g[q];
+    }
+    for (size_t i = 0; i < R.lm.size(); ++i) {
+        const int l = R.lm[i];
+        const double* r = &R.lm_rec[5 * i];
+        double A[3], g[2];
+        chi += bos::prior_landmark_terms<double>(c->lm[2 * (size_t)l], c->lm[2 * (size_t)l + 1], r, r + 2, A, g);
+        for (int q = 0; q < 3; ++q) hv[P.blk.off_ldiag + 3 * (int64_t)l + q] += A[q];
+        for (int q = 0; q < 2; ++q) c->b[3 * (size_t)c->NP + 2 * (size_t)l + q] += g[q];
+    }
     for (int k = 0; k < (int)c->o_src.size(); ++k)
         if (c->o_src[k] == c->o_dst[k]) {
             const double* z = &c->o_z[3 * (size_t)k];
@@ -305,6 +327,20 @@ void cpu_cost(const bos_cpu_gn* c, double& F, double& chi, int32_t& nrob) {
                               u[2] * e[0] + u[4] * e[1] + u[5] * e[2]};
         add(e[0] * Oe[0] + e[1] * Oe[1] + e[2] * Oe[2]);
     }
+    // priors are not robustified: F and chi^2 both gain rho
+    const bos::PriorSet& R = c->priors;
+    for (size_t i = 0; i < R.pose.size(); ++i) {
+        const double* p = &c->pose[3 * (size_t)R.pose[i]];
+        const double rho = bos::prior_pose_rho<double>(p[0], p[1], p[2], &R.pose_rec[9 * i], &R.pose_rec[9 * i + 3]);
+        chi += rho;
+        F += rho;
+    }
+    for (size_t i = 0; i < R.lm.size(); ++i) {
+        const double* l = &c->lm[2 * (size_t)R.lm[i]];
+        const double rho = bos::prior_landmark_rho<double>(l[0], l[1], &R.lm_rec[5 * i], &R.lm_rec[5 * i + 2]);
+        chi += rho;
+        F += rho;
+    }
 }
 
 }  // namespace
@@ -323,6 +359,16 @@ int bos_cpu_gn_step(bos_cpu_gn* c, double* chi2) {
 int bos_cpu_gn_set_kernel_threshold(bos_cpu_gn* c, double kt) {
     if (!c) return cfail(BOS_ERR_INVALID, "null handle");
     c->kt = kt;
+    return BOS_OK;
+}
+
+int bos_cpu_gn_set_priors(bos_cpu_gn* c, int32_t n_pose, const int32_t* pose, const double* pose_mean, const double* pose_omega,
+                          int32_t n_landmark, const int32_t* landmark, const double* landmark_mean,
+                          const double* landmark_omega) {
+    if (!c) return cfail(BOS_ERR_INVALID, "null handle");
+    const std::string err = bos::prior_set_build(c->NP, c->NL, c->plan.fixed, n_pose, pose, pose_mean, pose_omega, n_landmark,
+                                                 landmark, landmark_mean, landmark_omega, c->priors);
+    if (!err.empty()) return cfail(BOS_ERR_INVALID, "bos_cpu_gn_set_priors: " + err);
     return BOS_OK;
 }
 
